@@ -3,11 +3,13 @@
 
 Headline `value`: whole-job TRAINING images/sec (BASELINE.json configs[2]: B=64 per GPU,
 data-parallel over N GPUs with bucketed RCCL all-reduce overlapped with backward; fwd +
-loss + bwd + all-reduce + SGD-nesterov step).  The same line carries the single-GPU
-INFERENCE images/sec of configs[1] (B=32: forward + decode + class-wise NMS), the conv
-roofline of the dominant kernel family and the CPU-oracle baseline.
+loss + bwd + all-reduce + SGD-nesterov step).  A plain run sets up, warms up, times the K
+steps and prints that line (`--mode infer`: the inference line instead).  With `--full` the
+same line also carries the single-GPU INFERENCE images/sec of configs[1] (B=32: forward +
+decode + class-wise NMS), the rooflines of a profiled step, the YOLO-MS family and the
+CPU-oracle baselines.  `--dump-outputs DIR` writes what the last timed step computed.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 import argparse
@@ -59,7 +61,35 @@ def parse():
                          "normal priority, so the critical path wins CU arbitration)")
     ap.add_argument("--graph", type=int, default=0,
                     help="replay each step as one captured HIP graph (1 GPU; the plans are static)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the inference line next to the "
+                         "training one, the profiled step (rooflines, PMC traffic), the YOLO-MS family "
+                         "(--ms-version) and the CPU-oracle baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(float32; large arrays as a fixed seeded sample)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 20     # elements kept of an array larger than this (4 MiB as float32)
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as DIR/<name>.npy in float32.  An array of more than DUMP_SAMPLE
+    elements is written as the elements at DUMP_SAMPLE sorted flat indices drawn once from a CPU
+    generator seeded by the array's name and size, so two builds sample the same positions."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(f"{name}:{n}".encode()))
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(dirname, name + ".npy"), flat.float().cpu().numpy())
 
 
 def timed(fn, steps, warmup, world):
@@ -491,14 +521,18 @@ def main():
             crit = ComputeLoss(model.head, a.nc, dev, (a.size, a.size))
             tg = synth_targets(a.batch, a.nc, a.gts, 4321 + rank, dev)
 
+        last = {}     # --dump-outputs: the head maps and loss of the newest step
+
         def train_step():
             opt.zero_grad(set_to_none=True)
             outs = net(x)
             if a.loss == "compute":
-                loss = crit.loss_tensor(outs, tg)[0]      # device tensor: no host sync in the step
+                loss, terms = crit.loss_tensor(outs, tg)  # device tensors: no host sync in the step
             else:
                 # surrogate sum_i mean(o_i^2)
-                loss = sum(MeanSquare.apply(o) for o in outs)
+                loss, terms = sum(MeanSquare.apply(o) for o in outs), None
+            if a.dump_outputs:
+                last.update(outs=outs, loss=loss, terms=terms)
             loss.backward()
             opt.step()
 
@@ -511,16 +545,30 @@ def main():
         result["train"] = {"dt": dt, "med_ms": med, "graph": use_graph, "img_s": world * a.batch * a.steps / dt,
                            "peak_gb": torch.cuda.max_memory_allocated() / 2**30}
         log(f"[rank {rank}] train: {result['train']['img_s']:.1f} img/s ({dt / a.steps * 1e3:.1f} ms/step)")
-        if rank == 0 and not a.no_profile:
+        if rank == 0 and a.dump_outputs:
+            # what a caller of the step receives: the head maps, the loss and its terms, and the
+            # gradients and updated parameters the step left in the model (state_dict order)
+            named = list(model.named_parameters())
+            arrays = {f"train_head{i}": o for i, o in enumerate(last["outs"])}
+            arrays["train_loss"] = last["loss"]
+            if last["terms"] is not None:
+                arrays["train_loss_terms"] = last["terms"]
+            arrays["train_grads"] = torch.cat([p.grad.reshape(-1).float() for _, p in named if p.grad is not None])
+            arrays["train_params"] = torch.cat([p.detach().reshape(-1).float() for _, p in named])
+            dump_outputs(a.dump_outputs, arrays)
+            del arrays
+        if rank == 0 and a.full and not a.no_profile:
             _lib.profile_begin()
             train_step()
             prof = _lib.profile_end()
             result["train_prof"] = prof
+        last.clear()
         del opt, x
         torch.cuda.empty_cache()
 
     # ---------------- inference (configs[1]) ----------------
-    if rank == 0 and a.mode in ("both", "infer") and not a.no_infer:
+    # the headline of --mode infer; next to the training line it is part of --full
+    if rank == 0 and (a.mode == "infer" or (a.full and a.mode == "both")) and not a.no_infer:
         # a fresh random-init model (SURVEY 8d input set 1: ~8400 candidates/image, ~105/class);
         # the surrogate-trained weights above collapse every logit to ~0 (all classes tie).
         torch.manual_seed(0)
@@ -532,17 +580,21 @@ def main():
 
         nms_stream = torch.cuda.Stream(device=dev) if a.nms_overlap else None
 
+        ilast = {}    # --dump-outputs: the decoded output and NMS results of the newest batch
+
         def infer_step():
             y = imodel(xi)
             if nms_stream is None:
-                yops.batched_nms_indices(y, 0.25, 0.45)
-                return
-            # serving pipeline: batch k's decode output goes to class-wise NMS on a second stream
-            # while batch k+1's forward runs (the greedy NMS of a big segment holds one CU)
-            nms_stream.wait_stream(torch.cuda.current_stream(dev))
-            y.record_stream(nms_stream)
-            with torch.cuda.stream(nms_stream):
-                yops.batched_nms_indices(y, 0.25, 0.45)
+                det = yops.batched_nms_indices(y, 0.25, 0.45)
+            else:
+                # serving pipeline: batch k's decode output goes to class-wise NMS on a second stream
+                # while batch k+1's forward runs (the greedy NMS of a big segment holds one CU)
+                nms_stream.wait_stream(torch.cuda.current_stream(dev))
+                y.record_stream(nms_stream)
+                with torch.cuda.stream(nms_stream):
+                    det = yops.batched_nms_indices(y, 0.25, 0.45)
+            if a.dump_outputs:
+                ilast.update(y=y, det=det)
 
         run_infer = graphed(infer_step, a.warmup) if a.graph else infer_step
         dti, medi = timed(run_infer, a.steps, a.warmup, 1)
@@ -551,12 +603,21 @@ def main():
         result["infer"] = {"dt": dti, "med_ms": medi, "graph": bool(a.graph),
                            "img_s": a.infer_batch * a.steps / dti}
         log(f"[rank 0] infer: {result['infer']['img_s']:.1f} img/s ({dti / a.steps * 1e3:.2f} ms/batch)")
-        if not a.no_profile:
+        if a.dump_outputs:
+            bxy, score, keep, klbl, cnt = ilast["det"]
+            # entries of keep / keep_lbl past counts[b] are unwritten memory: dump them as -1
+            valid = torch.arange(keep.shape[1], device=dev)[None, :] < cnt[:, None]
+            dump_outputs(a.dump_outputs, {
+                "infer_pred": ilast["y"], "infer_boxes": bxy, "infer_scores": score,
+                "infer_keep": torch.where(valid, keep, -1), "infer_keep_labels": torch.where(valid, klbl, -1),
+                "infer_counts": cnt})
+        ilast.clear()
+        if a.full and not a.no_profile:
             _lib.profile_begin()
             infer_step()
             result["infer_prof"] = _lib.profile_end()
 
-    if rank == 0 and world == 1 and a.ms_version != "none" and not a.version.startswith("ms-"):
+    if a.full and rank == 0 and world == 1 and a.ms_version != "none" and not a.version.startswith("ms-"):
         result["ms"] = measure_ms_family(a, dev, dtype)
 
     if rank == 0:
@@ -612,7 +673,7 @@ def main():
                                   "parallelism": "replica"}
         if "ms" in result:
             line["ms_family"] = result["ms"]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             log("[rank 0] cpu baseline (oracle on host cores)...")
             if "train" in result:
                 line["cpu_baseline"] = cpu_baseline_train(a.version, a.nc, a.size, loss=a.loss, gts=a.gts)

@@ -16,7 +16,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for mode in $MODES; do
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$mode" -o run -- \
-    python3 "$ROOT/bench.py" --mode $mode --steps 10 --warmup 3 --no-cpu-baseline --ms-version none $EXTRA > "$OUT/bench_$mode.json" 2> "$OUT/bench_$mode.err"
+    python3 "$ROOT/bench.py" --full --mode $mode --steps 10 --warmup 3 --no-cpu-baseline --ms-version none $EXTRA > "$OUT/bench_$mode.json" 2> "$OUT/bench_$mode.err"
 done
 echo "stats done"
 # PMC passes per mode (FETCH_SIZE and WRITE_SIZE do not fit one TCC pass on gfx950)
