@@ -321,3 +321,173 @@ def test_affine_act_matches_fp64(npix, c, ld, dt, res_mode):
 
 def F_silu(a):
     return a * torch.sigmoid(a)
+
+
+# ---- yms_bn_finalize / yms_bn_finalize_ld from a synthetic statistics table ------------------------
+def _fin_ranges(rows):
+    """(rows per pre-reduced range, ranges) of yms_bn_finalize_ld's in-place pre-reduction"""
+    if rows <= 1024:
+        return rows, 1
+    s = min(256, -(-rows // 64))
+    rs = -(-rows // s)
+    return rs, -(-rows // rs)
+
+
+def _fin_table(rows, c, pattern, seed):
+    """Per row r a pixel count n_r (0: empty), a mean and an M2 per channel; stored as the producers
+    store them: s1 = float32(n_r * mean_r), m2 = float32(M2_r); empty rows hold NaN moments.
+    Per-channel |mean| / std from 1 to 1e3, std from 0.1 to 10."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    n = rng.integers(1, 129, rows).astype(np.float64)
+    rs, nr = _fin_ranges(rows)
+    if pattern == "random":              # about 20% of the rows empty
+        n[rng.random(rows) < 0.2] = 0
+    elif pattern == "head":              # the first 150 rows empty: K comes from a later row (and range)
+        n[:150 if rows > 300 else rows // 2] = 0
+    else:                                # one whole pre-reduced range in the middle empty
+        k = nr // 2
+        n[k * rs:(k + 1) * rs] = 0 if nr > 1 else n[k * rs:(k + 1) * rs]
+        if nr == 1:
+            n[rows // 3:rows // 2] = 0
+    if not (n > 0).any():
+        n[-1] = 1
+    std = 10.0 ** rng.uniform(-1, 1, c)
+    mu = std * 10.0 ** rng.uniform(0, 3, c) * rng.choice([-1.0, 1.0], c)
+    mu[0] = 1e3 * std[0]
+    nn = np.maximum(n, 1)[:, None]
+    mean_r = mu + std * rng.standard_normal((rows, c)) / np.sqrt(nn)
+    m2_r = std ** 2 * nn * rng.uniform(0.5, 1.5, (rows, c))
+    s1 = (n[:, None] * mean_r).astype(np.float32)
+    m2 = m2_r.astype(np.float32)
+    s1[n == 0] = np.nan
+    m2[n == 0] = np.nan
+    return s1, m2, n.astype(np.float32)
+
+
+def _fin_reference(s1, m2, n, emulate):
+    """(mean, biased var, N) per channel.  emulate=False: the exact fp64 merge of the table as stored
+    (row mean = s1 / n_r in fp64, Chan's formula).  emulate=True: the documented merge -- row means
+    formed in fp32, shifted by the first non-empty row's mean, fp64 everywhere else."""
+    import numpy as np
+    keep = n > 0
+    s1, m2, n = s1[keep], m2[keep], n[keep]
+    N = n.astype(np.float64).sum()
+    nd = n.astype(np.float64)[:, None]
+    if not emulate:
+        mr = s1.astype(np.float64) / nd
+        mean = s1.astype(np.float64).sum(0) / N
+        return mean, (m2.astype(np.float64) + nd * (mr - mean) ** 2).sum(0) / N, N
+    mr = (s1 / n[:, None]).astype(np.float32).astype(np.float64)      # fp32 division, as the kernels do
+    K = mr[0]
+    d = mr - K
+    d1 = (nd * d).sum(0)
+    d2 = (m2.astype(np.float64) + nd * d * d).sum(0)
+    return K + d1 / N, (d2 - d1 * d1 / N) / N, N
+
+
+def _fin_expected(mean, var, N, gam, bet, rm0, rv0, eps, mom):
+    istd = 1.0 / (var + eps) ** 0.5
+    sc = gam * istd
+    return dict(mean=mean, istd=istd, sc=sc, sh=bet - mean * sc, rm=(1 - mom) * rm0 + mom * mean,
+                rv=(1 - mom) * rv0 + mom * var * N / max(N - 1, 1), var=var)
+
+
+def _fin_errors(got, ref, gam, bet, rm0, eps, mom):
+    """errors in the units of test_bn_stats_large_mean_conv_and_dw's gates (scale like invstd; shift and
+    running_mean relative to the magnitudes of the terms they are the sum of)"""
+    import numpy as np
+    sd = np.sqrt(ref["var"] + eps)
+    e = {"mean": np.abs(got["mean"] - ref["mean"]) / np.abs(ref["mean"]),
+         "istd": np.abs(got["istd"] - ref["istd"]) * sd,
+         "sc": np.abs(got["sc"] - ref["sc"]) * sd / np.abs(gam),
+         "sh": np.abs(got["sh"] - ref["sh"]) / (np.abs(bet) + np.abs(ref["mean"] * ref["sc"]))}
+    if "rv" in got:
+        e["rv"] = np.abs(got["rv"] - ref["rv"]) / ref["rv"]
+        e["rm"] = np.abs(got["rm"] - ref["rm"]) / (np.abs((1 - mom) * rm0) + np.abs(mom * ref["mean"]))
+    return {k: float(v.max()) for k, v in e.items()}
+
+
+FIN_TOL = {"mean": 1e-6, "istd": 1e-4, "sc": 1e-4, "sh": 1e-4, "rv": 1e-5, "rm": 1e-6}
+FIN_CASES = [(rows, c) for rows in (1, 31, 33, 1024, 1025, 4099, 20000) for c in (1, 8, 20, 65, 200)
+             if rows < 20000 or c <= 65]
+
+
+@pytest.mark.parametrize("rows,c", FIN_CASES)
+def test_bn_finalize_from_synthetic_table(rows, c):
+    """yms_bn_finalize_ld on a statistics table built on the host -- [rows][2][stats_ld] moments then
+    [rows] counts -- against the exact fp64 merge of the table as stored: mean 1e-6 relative, invstd
+    (and scale) 1e-4 relative, running_var 1e-5 relative, shift / running_mean against the terms they
+    sum (the gates of test_bn_stats_large_mean_conv_and_dw).  rows cover the 32-lane small kernel's
+    edges (1, 31, 33, 1024), the first pre-reduced table (1025: 17 ranges of 61 rows) and the capped
+    one (20000: 254 ranges of 79 rows); stats_ld = r8(c) and r8(c) + 8; mi_ld = c and c + 24 (exactly
+    [0, c) and [mi_ld, mi_ld + c) of the NaN-filled mean_invstd are written); running buffers given
+    and NULL; empty rows (NaN moments, count 0) at random, as the first 150 rows (the shift K then
+    comes from a later row and the first pre-reduced range is empty) and as one whole pre-reduced
+    range.  yms_bn_finalize must equal yms_bn_finalize_ld(mi_ld = c) bit for bit.  Each call gets a
+    fresh copy of the table (the pre-reduction writes in place).
+    Per-channel |mean| / std goes up to 1e3 with no reduction of the offsets: a numpy emulation of
+    the documented merge (fp32 row means, fp64 elsewhere) stays within half of every gate, asserted
+    below; its worst figures over all cases are mean 5.8e-8, invstd / scale / shift 1.4e-6,
+    running_var 1.7e-6, running_mean 5.2e-8 (the fp32 rounding of the row means; storing the
+    outputs as fp32 adds at most 6e-8)."""
+    import numpy as np
+    from hiputil import r8
+    eps, mom = 1e-3, 0.03
+    eps64 = float(np.float32(eps))
+    mom64 = float(np.float32(mom))
+    rng = np.random.default_rng(rows * 1000 + c)
+    gam = rng.uniform(0.5, 1.5, c).astype(np.float32)
+    bet = rng.standard_normal(c).astype(np.float32)
+    rm0 = rng.standard_normal(c).astype(np.float32)
+    rv0 = rng.uniform(0.5, 1.5, c).astype(np.float32)
+    gd, bd = torch.from_numpy(gam).cuda(), torch.from_numpy(bet).cuda()
+    f64 = [a.astype(np.float64) for a in (gam, bet, rm0, rv0)]
+    for pattern in ("random", "head", "range"):
+        s1, m2, n = _fin_table(rows, c, pattern, rows + c + len(pattern))
+        assert (n > 0).any()
+        ref = _fin_expected(*_fin_reference(s1, m2, n, False), *f64, eps64, mom64)
+        emu = _fin_expected(*_fin_reference(s1, m2, n, True), *f64, eps64, mom64)
+        ee = _fin_errors(emu, ref, f64[0], f64[1], f64[2], eps64, mom64)
+        assert all(ee[k] <= 0.5 * FIN_TOL[k] for k in ee), ee
+        count = int(n.astype(np.float64).sum())
+        for sld in (r8(c), r8(c) + 8):
+            tab = np.full((rows, 2, sld), 7.0, dtype=np.float32)      # 7.0 in the columns past c
+            tab[:, 0, :c], tab[:, 1, :c] = s1, m2
+            host = torch.from_numpy(np.concatenate([tab.reshape(-1), n]))
+            for mi_ld in (c, c + 24):
+                for with_running in (True, False):
+                    outs = []
+                    for fn in ("yms_bn_finalize_ld", "yms_bn_finalize") if mi_ld == c else ("yms_bn_finalize_ld",):
+                        st = host.cuda()
+                        mi = torch.full((2 * mi_ld + 16,), float("nan"), device="cuda")
+                        scsh = torch.full((2, c + 8), float("nan"), device="cuda")
+                        run = torch.full((2, c + 8), 7.0, device="cuda")
+                        run[0, :c], run[1, :c] = torch.from_numpy(rm0).cuda(), torch.from_numpy(rv0).cuda()
+                        rp = (run[0].data_ptr(), run[1].data_ptr()) if with_running else (None, None)
+                        args = [c, st.data_ptr(), rows, sld, count, gd.data_ptr(), bd.data_ptr(), *rp,
+                                ctypes.c_float(mom), ctypes.c_float(eps), mi.data_ptr()]
+                        args += [mi_ld] if fn.endswith("_ld") else []
+                        L.call(fn, *args, scsh[0].data_ptr(), scsh[1].data_ptr(), L.stream_ptr())
+                        torch.cuda.synchronize()
+                        outs.append((mi, scsh, run))
+                    mi, scsh, run = outs[0]
+                    key = (pattern, sld, mi_ld, with_running)
+                    if len(outs) == 2:
+                        for a, b in zip(outs[0], outs[1]):
+                            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), key
+                    written = torch.zeros(2 * mi_ld + 16, dtype=torch.bool)
+                    written[:c] = True
+                    written[mi_ld:mi_ld + c] = True
+                    assert torch.equal(torch.isnan(mi).cpu(), ~written), key
+                    assert torch.isnan(scsh[:, c:]).all() and torch.isfinite(scsh[:, :c]).all(), key
+                    assert (run[:, c:] == 7.0).all(), key
+                    got = dict(mean=mi[:c], istd=mi[mi_ld:mi_ld + c], sc=scsh[0, :c], sh=scsh[1, :c])
+                    if with_running:
+                        got.update(rm=run[0, :c], rv=run[1, :c])
+                    else:
+                        assert torch.equal(run[0, :c].cpu(), torch.from_numpy(rm0)), key
+                        assert torch.equal(run[1, :c].cpu(), torch.from_numpy(rv0)), key
+                    got = {k: v.double().cpu().numpy() for k, v in got.items()}
+                    err = _fin_errors(got, ref, f64[0], f64[1], f64[2], eps64, mom64)
+                    assert all(err[k] <= FIN_TOL[k] for k in err), (key, err)

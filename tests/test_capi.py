@@ -188,3 +188,66 @@ def test_dwconv_host_sizing_follows_the_kernel_selection():
         assert b // row <= units
     assert ws(sh(64, 40, 40, 288, 7, L.BF16)) < ws(sh(64, 40, 40, 288, 7, L.F32))   # fp32: tile kernel rows
     assert ws(sh(2, 13, 9, 12, 9, L.BF16)) == 0                                    # C % 8 != 0: rejected
+
+
+def test_glue_decode_finalize_argument_validation():
+    """Argument checks of the layout / cast / upsample / decode / finalize / pack entry points: each row
+    is a valid call with ONE argument broken, and returns YMS_ERR_INVALID before any launch (no GPU
+    needed: the pointers are host dummies that are never dereferenced)."""
+    buf = (ctypes.c_float * 16)()
+    P = ctypes.addressof(buf)
+    lib = L.lib()
+    B, BAD_DT = L.BF16, 7
+
+    def rows(name, good, **broken):
+        """good: {arg name: value} in call order; broken: {label: {arg name: bad value}}"""
+        fn = getattr(lib, name)
+        for label, change in broken.items():
+            assert set(change) <= set(good), (name, label)
+            args = [change.get(k, v) for k, v in good.items()]
+            assert fn(*args) == 1, (name, label)
+
+    up = dict(dtype=B, n=1, h=4, w=4, c=16, x=P, x_ld=32, x_off=8, y=P, y_ld=32, y_off=8, stream=None)
+    for name in ("yms_upsample2x_fwd", "yms_upsample2x_bwd"):
+        good = dict(up) if name.endswith("fwd") else dict(list(up.items())[:-1] + [("acc", 0), ("stream", None)])
+        rows(name, good, x_ld=dict(x_ld=36), y_ld=dict(y_ld=36), x_off=dict(x_off=4), y_off=dict(y_off=4),
+             x_over=dict(x_off=24), y_over=dict(y_off=24), dtype=dict(dtype=BAD_DT), n=dict(n=0), c=dict(c=0),
+             x_null=dict(x=None), y_null=dict(y=None))
+    rows("yms_pack_input", dict(dtype=B, n=1, c=3, h=4, w=4, x=P, y=P, ld=8, stream=None),
+         ld=dict(ld=12), ld_small=dict(c=9), dtype=dict(dtype=BAD_DT), n=dict(n=0), x_null=dict(x=None))
+    rows("yms_nhwc_to_nchw", dict(dtype=B, dtype_nchw=L.F32, n=1, h=4, w=4, c=16, x=P, ld=32, off=8, y=P, stream=None),
+         ld=dict(ld=36), off=dict(off=4), over=dict(off=24), dtype=dict(dtype=BAD_DT), dtype_nchw=dict(dtype_nchw=BAD_DT),
+         n=dict(n=0), h=dict(h=0), c=dict(c=0), x_null=dict(x=None), y_null=dict(y=None))
+    rows("yms_nchw_to_nhwc", dict(dtype_nchw=L.F32, dtype=B, n=1, h=4, w=4, c=16, x=P, y=P, ld=32, off=8, acc=0,
+                                  stream=None),
+         ld=dict(ld=36), off=dict(off=4), over=dict(off=24), dtype=dict(dtype=BAD_DT), dtype_nchw=dict(dtype_nchw=-1),
+         n=dict(n=0), w=dict(w=0), c=dict(c=0), x_null=dict(x=None), y_null=dict(y=None))
+    rows("yms_cast", dict(di=L.F32, do=B, count=16, x=P, y=P, stream=None),
+         count0=dict(count=0), count_neg=dict(count=-5), di=dict(di=3), do=dict(do=BAD_DT), x_null=dict(x=None))
+    lv = (ctypes.c_void_p * 5)(*([P] * 5))
+    hs = (ctypes.c_int * 5)(*([2] * 5))
+    st = (ctypes.c_float * 5)(*([8.0] * 5))
+    rows("yms_head_decode", dict(dtype=B, n=1, nc=80, nlev=3, lvl=lv, hs=hs, ws=hs, no_ld=144, strides=st, out=P,
+                                 conf=ctypes.c_float(0.25), bxy=P, score=P, label=P, stream=None),
+         no_ld_small=dict(no_ld=136), no_ld_mod8=dict(no_ld=148), nlev5=dict(nlev=5), nlev0=dict(nlev=0),
+         score_without_label=dict(label=None), score_without_boxes=dict(bxy=None), dtype=dict(dtype=BAD_DT),
+         nc=dict(nc=0), out_null=dict(out=None))
+    rows("yms_dfl", dict(dtype=B, n=1, A=8, ch=16, x=P, out=P, stream=None), dtype=dict(dtype=BAD_DT), A=dict(A=0),
+         ch=dict(ch=0))
+    fin = dict(c=16, stats=P, rows=4, stats_ld=16, count=64, gamma=P, beta=P, rmean=P, rvar=P,
+               momentum=ctypes.c_float(0.03), eps=ctypes.c_float(1e-3), mi=P, mi_ld=16, scale=P, shift=P, stream=None)
+    rows("yms_bn_finalize_ld", fin, stats_ld=dict(stats_ld=8), mi_ld=dict(mi_ld=8), count=dict(count=0),
+         rows=dict(rows=0), c=dict(c=0), stats_null=dict(stats=None), mi_null=dict(mi=None))
+    rows("yms_bn_finalize", {k: v for k, v in fin.items() if k != "mi_ld"}, stats_ld=dict(stats_ld=8),
+         count=dict(count=-1), rows=dict(rows=0))
+    rows("yms_bn_fold", dict(c=8, gamma=P, beta=P, rmean=P, rvar=P, eps=ctypes.c_float(1e-3), scale=P, shift=P,
+                             stream=None),
+         c=dict(c=0), gamma_without_beta=dict(beta=None), gamma_without_rvar=dict(rvar=None), scale_null=dict(scale=None))
+    rows("yms_conv_pack_weights_batched", dict(njobs=2, jobs=P, base=None, stream=None), njobs=dict(njobs=-1),
+         jobs_null=dict(jobs=None))
+    # stride-2 dgrad weights keep the parity-class single pack
+    sh = L.ConvShape(1, 8, 8, 16, 32, 3, 2, 1, 4, 4, L.BF16)
+    job = L.PackJob()
+    assert lib.yms_pack_job_init(ctypes.pointer(sh), P, None, 1, ctypes.byref(job)) == 2
+    assert lib.yms_pack_job_init(ctypes.pointer(sh), P, None, 0, ctypes.byref(job)) == 0
+    assert lib.yms_pack_job_init(ctypes.pointer(sh), None, None, 0, ctypes.byref(job)) == 1

@@ -1204,7 +1204,7 @@ yms_status yms_pack_input(int dtype, int n, int c, int h, int w, const float* x,
 
 yms_status yms_nhwc_to_nchw(int dtype, int dtype_nchw, int n, int h, int w, int c, const void* x,
                             int ld, int off, void* y, void* stream) {
-  if (n <= 0 || !x || !y || ld < off + c) return YMS_ERR_INVALID;
+  if (n <= 0 || h <= 0 || w <= 0 || !x || !y || !vok(ld, off, c)) return YMS_ERR_INVALID;
   const long hw = (long)h * w;
   dim3 grid((unsigned)cdiv(hw, 64), (unsigned)cdiv(c, 64), (unsigned)n);
   YMS_DT2(dtype, dtype_nchw, TI, TO, hipLaunchKernelGGL((nhwc_to_nchw_kernel<TI, TO>), grid, dim3(256), 0,
@@ -1215,7 +1215,7 @@ yms_status yms_nhwc_to_nchw(int dtype, int dtype_nchw, int n, int h, int w, int 
 
 yms_status yms_nchw_to_nhwc(int dtype_nchw, int dtype, int n, int h, int w, int c, const void* x,
                             void* y, int ld, int off, int accumulate, void* stream) {
-  if (n <= 0 || !x || !y || ld < off + c) return YMS_ERR_INVALID;
+  if (n <= 0 || h <= 0 || w <= 0 || !x || !y || !vok(ld, off, c)) return YMS_ERR_INVALID;
   const long hw = (long)h * w;
   dim3 grid((unsigned)cdiv(hw, 64), (unsigned)cdiv(c, 64), (unsigned)n);
   YMS_DT2(dtype_nchw, dtype, TI, TO, hipLaunchKernelGGL((nchw_to_nhwc_kernel<TI, TO>), grid, dim3(256), 0,
