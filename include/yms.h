@@ -275,6 +275,27 @@ yms_status yms_map_match(int n_images, const float* det_boxes, const float* det_
 yms_status yms_map_accumulate(int n_det, const float* scores, const int* labels, const int* image,
                               const uint8_t* tp, const uint8_t* kept, int n_classes, const int* n_gt,
                               double* ap, double* map);
+/* ---- COCO AP: mAP@[.5:.95], AP by object size, AR@1/10/100 (torchmetrics' default construction) ---- */
+/* GPU: the matching of yms_map_match for n_thr (1..16) increasing IoU thresholds in (0, 1]
+ * (iou_thrs: HOST array) times COCOeval's four area ranges all / small / medium / large
+ * ([0,1e10], [0,32^2], [32^2,96^2], [96^2,1e10], both ends inclusive, area = w*h), bbox, no crowd:
+ * out-of-range ground truths are ignore (visited after the in-range ones, taken only when no in-range
+ * one qualifies); a detection matched to one, or unmatched and itself out of range, is ignored.
+ *   matched[a * n_det + d], ignored[a * n_det + d]: bit t = at threshold t (area range a)
+ *   gt_ignore[g]: bit a = ground truth g is out of area range a
+ *   rank_ws: 2 * n_det ints; the first n_det receive the per-class rank (kept = rank < 100)
+ * n_det = det_off[n_images].  max_gt_per_image <= 2048 (else YMS_ERR_UNSUPPORTED). */
+yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, const float* det_scores,
+                              const int* det_labels, const int* det_off, const float* gt_boxes, const int* gt_labels,
+                              const int* gt_off, int n_thr, const double* iou_thrs, uint16_t* matched,
+                              uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws, int max_gt_per_image,
+                              void* stream);
+/* HOST (not stream-ordered; host arrays in evaluation order): COCOeval.accumulate for maxDets
+ * 1 / 10 / 100 -> precision[n_thr][101][n_classes][4][3] and recall[n_thr][n_classes][4][3], -1 where
+ * npig[class * 4 + area] (the number of non-ignored ground truths) is 0. */
+yms_status yms_map_accumulate_coco(int n_det, const float* scores, const int* labels, const int* image,
+                                   const int* rank, const uint16_t* matched, const uint16_t* ignored, int n_thr,
+                                   int n_classes, const int* npig, double* precision, double* recall);
 
 /* ---- input pipeline ------------------------------------------------------ */
 /* dataset.py:132-134 per-sample A.Resize(INTER_LINEAR) + A.Normalize(mean, std) + ToTensorV2 and

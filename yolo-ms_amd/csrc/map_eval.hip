@@ -9,6 +9,11 @@
 //   detection taking the unmatched ground truth of highest IoU (ties -> the later one);
 //   per class: kept detections ordered by (score desc, image, input index), tp/fp cumsums,
 //   precision made monotone, 101-point interpolation; mAP = mean over classes with ground truth.
+// COCO AP (mAP@[.5:.95], AP by object size, AR@1/10/100): map_match_coco_kernel runs the same matching
+// for up to 16 IoU thresholds x the four COCOeval area ranges at once, one (threshold, area) pair per
+// lane, with COCOeval's ignore rules (out-of-range ground truths are visited last and only taken when
+// no in-range one qualifies; a detection matched to one, or unmatched and itself out of range, is
+// ignored); yms_map_accumulate_coco fills COCOeval's precision / recall tables on the host.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -112,6 +117,174 @@ __global__ __launch_bounds__(64) void map_match_kernel(const float* dbox, const 
   }
 }
 
+// ---- COCO matching: T thresholds x 4 area ranges ------------------------------------------------
+constexpr int MAP_MAX_THR = 16;
+constexpr int MAP_N_AREA = 4;
+constexpr int MAP_COCO_WAVES = 4;
+
+struct MapCocoThr {
+  double thr[MAP_MAX_THR];
+  int n;
+};
+
+// COCOeval's areaRng all / small / medium / large, both ends inclusive: bit a set = out of range a
+__device__ __forceinline__ unsigned map_area_out_bits(double area) {
+  unsigned b = 0;
+  if (area < 0.0 || area > 1e10) b |= 1u;
+  if (area < 0.0 || area > 1024.0) b |= 2u;
+  if (area < 1024.0 || area > 9216.0) b |= 4u;
+  if (area < 9216.0 || area > 1e10) b |= 8u;
+  return b;
+}
+
+// maskUtils.iou on xywh doubles, every product and sum rounded on its own as numpy does
+__device__ __forceinline__ double map_iou_xywh(double bx, double by, double bw, double bh, double gx, double gy,
+                                               double gw, double gh) {
+#pragma clang fp contract(off)
+  const double w = fmin(bx + bw, gx + gw) - fmax(bx, gx);
+  const double h = fmin(by + bh, gy + gh) - fmax(by, gy);
+  if (!(w > 0.0 && h > 0.0)) return 0.0;
+  const double inter = w * h;
+  const double a = bw * bh, b = gw * gh;
+  return inter / (a + b - inter);
+}
+
+// One workgroup (4 waves) per image.  Setup: the image's ground truths are staged in LDS as xywh
+// doubles ordered by (class, input index), so a class is one contiguous segment in COCOeval's
+// visiting order; detections are ranked within their class and listed by (class, rank) in order_ws.
+// Matching: the waves take the image's ground-truth classes in turn; lane = area * 16 + threshold
+// runs its own greedy matching over the class's <= 100 kept detections.  Per detection the wave
+// computes the IoUs against the segment 64 ground truths at a time and broadcasts only those that
+// reach the lowest threshold; each lane keeps the best unmatched in-range and out-of-range candidate
+// (later one on ties) and takes the in-range one if there is any (COCOeval's break).  The "already
+// matched" bits are one LDS word column per lane (gm[wave][word][lane]): no lane shares a word, and
+// classes own disjoint bits, so they are cleared once.  There is no barrier after the setup.
+__global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
+    const float* dbox, const float* dscore, const int* dlabel, const int* doff, const float* gbox, const int* glabel,
+    const int* goff, MapCocoThr P, long n_det, uint16_t* dmatch, uint16_t* dign, uint8_t* gign_out, int* rank_out,
+    int* order_ws) {
+  __shared__ double gb[MAP_MAX_GT][4];
+  __shared__ int gl[MAP_MAX_GT];
+  __shared__ int heads[MAP_MAX_GT];
+  __shared__ uint8_t gig[MAP_MAX_GT];
+  __shared__ unsigned gm[MAP_COCO_WAVES][MAP_MAX_GT / 32][64];
+  __shared__ int n_heads;
+  constexpr int NT = 64 * MAP_COCO_WAVES;
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d0 = doff[img], nd = doff[img + 1] - d0;
+  const int g0 = goff[img], ng = goff[img + 1] - g0;
+  if (ng > MAP_MAX_GT) return;            // the host entry point refuses these; never index past the LDS arrays
+  const int T = P.n;
+  const unsigned tmask = (1u << T) - 1u;
+  if (tid == 0) n_heads = 0;
+  // ground truths -> LDS in (class, input index) order, with their area-ignore bits
+  for (int j = tid; j < ng; j += NT) {
+    const int lab = glabel[g0 + j];
+    int p = 0;
+    for (int i = 0; i < ng; ++i) {
+      const int li = glabel[g0 + i];
+      p += (li < lab || (li == lab && i < j)) ? 1 : 0;
+    }
+    const float* q = gbox + (long)(g0 + j) * 4;
+    const double gw = (double)(q[2] - q[0]), gh = (double)(q[3] - q[1]);   // width / height in fp32, as box_convert
+    gb[p][0] = (double)q[0];
+    gb[p][1] = (double)q[1];
+    gb[p][2] = gw;
+    gb[p][3] = gh;
+    gl[p] = lab;
+    const unsigned bits = map_area_out_bits(gw * gh);
+    gig[p] = (uint8_t)bits;
+    gign_out[g0 + j] = (uint8_t)bits;
+  }
+  for (int w = 0; w < (ng + 31) / 32; ++w) gm[wave][w][lane] = 0u;
+  // detections: rank within the class (stable descending score), position in (class, rank) order,
+  // and the masks of an unmatched detection (classes without ground truth here keep them)
+  for (int d = tid; d < nd; d += NT) {
+    const int lab = dlabel[d0 + d];
+    const float sc = dscore[d0 + d];
+    int r = 0, below = 0;
+    for (int j = 0; j < nd; ++j) {
+      const int lj = dlabel[d0 + j];
+      below += lj < lab ? 1 : 0;
+      if (lj != lab) continue;
+      const float sj = dscore[d0 + j];
+      r += (sj > sc || (sj == sc && j < d)) ? 1 : 0;
+    }
+    rank_out[d0 + d] = r;
+    order_ws[d0 + below + r] = d;
+    const float* bp = dbox + (long)(d0 + d) * 4;
+    const unsigned out = map_area_out_bits((double)(bp[2] - bp[0]) * (double)(bp[3] - bp[1]));
+#pragma unroll
+    for (int a = 0; a < MAP_N_AREA; ++a) {
+      dmatch[a * n_det + d0 + d] = 0;
+      dign[a * n_det + d0 + d] = (uint16_t)(((out >> a) & 1u) ? tmask : 0u);
+    }
+  }
+  __syncthreads();
+  for (int p = tid; p < ng; p += NT)
+    if (p == 0 || gl[p] != gl[p - 1]) heads[atomicAdd(&n_heads, 1)] = p;
+  __syncthreads();
+  const int nh = n_heads;
+
+  const int t = lane & 15, a = lane >> 4;
+  const bool live = t < T;
+  const double thr_l = fmin(P.thr[live ? t : 0], 1.0 - 1e-10);
+  const double thr_min = fmin(P.thr[0], 1.0 - 1e-10);      // thresholds are increasing
+  for (int h = wave; h < nh; h += MAP_COCO_WAVES) {
+    const int gs = heads[h], c = gl[gs];
+    int gn = 0;
+    for (int base = gs; base < ng; base += 64) {
+      const unsigned long long same = __ballot(base + lane < ng && gl[min(base + lane, ng - 1)] == c);
+      gn += __popcll(same);
+      if (same != ~0ull) break;
+    }
+    int ds = 0, dn = 0;
+    for (int base = 0; base < nd; base += 64) {
+      const int lj = base + lane < nd ? dlabel[d0 + base + lane] : 0x7fffffff;
+      ds += __popcll(__ballot(lj < c));
+      dn += __popcll(__ballot(lj == c));
+    }
+    const int nr = min(dn, MAP_MAXDET);
+    for (int r = 0; r < nr; ++r) {
+      const int d = order_ws[d0 + ds + r];
+      if ((unsigned)d >= (unsigned)nd) continue;      // NaN scores leave holes in the order: never index by one
+      const float* bp = dbox + (long)(d0 + d) * 4;
+      const double bx = (double)bp[0], by = (double)bp[1];
+      const double bw = (double)(bp[2] - bp[0]), bh = (double)(bp[3] - bp[1]);
+      const bool d_out = (map_area_out_bits(bw * bh) >> a) & 1u;
+      double best_n = thr_l, best_i = thr_l;      // in-range / out-of-range (ignored) ground truths
+      int jn = -1, ji = -1;
+      for (int base = 0; base < gn; base += 64) {
+        const int p = gs + base + lane;
+        double iou = 0.0;
+        if (base + lane < gn) iou = map_iou_xywh(bx, by, bw, bh, gb[p][0], gb[p][1], gb[p][2], gb[p][3]);
+        unsigned long long cand = __ballot(base + lane < gn && iou >= thr_min);
+        while (cand) {                                 // wave-uniform: candidates in visiting order
+          const int src = __ffsll((long long)cand) - 1;
+          cand &= cand - 1;
+          const double ci = __shfl(iou, src);
+          const int cp = gs + base + src;
+          if (!live || ((gm[wave][cp >> 5][lane] >> (cp & 31)) & 1u)) continue;
+          if ((gig[cp] >> a) & 1u) {
+            if (ci >= best_i) { best_i = ci; ji = cp; }
+          } else {
+            if (ci >= best_n) { best_n = ci; jn = cp; }
+          }
+        }
+      }
+      const int m = jn >= 0 ? jn : ji;
+      const bool matched = live && m >= 0;
+      if (matched) gm[wave][m >> 5][lane] |= 1u << (m & 31);
+      const bool ign = live && (matched ? jn < 0 : d_out);
+      const unsigned long long bm = __ballot(matched), bi = __ballot(ign);
+      if (lane < MAP_N_AREA) {
+        dmatch[lane * n_det + d0 + d] = (uint16_t)((bm >> (16 * lane)) & 0xffffull);
+        dign[lane * n_det + d0 + d] = (uint16_t)((bi >> (16 * lane)) & 0xffffull);
+      }
+    }
+  }
+}
+
 }  // namespace yms
 
 using namespace yms;
@@ -193,6 +366,89 @@ yms_status yms_map_accumulate(int n_det, const float* scores, const int* labels,
     aps.push_back(ap[c]);
   }
   *map = aps.empty() ? -1.0 : np_pairwise_sum(aps.data(), (long)aps.size()) / (double)aps.size();
+  return YMS_OK;
+}
+
+// T thresholds x 4 area ranges in one launch (COCOeval.evaluateImg, bbox, no crowd)
+yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, const float* det_scores,
+                              const int* det_labels, const int* det_off, const float* gt_boxes, const int* gt_labels,
+                              const int* gt_off, int n_thr, const double* iou_thrs, uint16_t* matched,
+                              uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws, int max_gt_per_image,
+                              void* stream) {
+  if (n_thr < 1 || n_thr > MAP_MAX_THR || !iou_thrs) return YMS_ERR_INVALID;
+  MapCocoThr P;
+  for (int t = 0; t < MAP_MAX_THR; ++t) P.thr[t] = t < n_thr ? iou_thrs[t] : 2.0;
+  P.n = n_thr;
+  for (int t = 0; t < n_thr; ++t)
+    if (!(P.thr[t] > 0.0 && P.thr[t] <= 1.0) || (t > 0 && !(P.thr[t] > P.thr[t - 1]))) return YMS_ERR_INVALID;
+  if (n_images <= 0) return YMS_OK;
+  if (n_det < 0 || !det_off || !gt_off) return YMS_ERR_INVALID;
+  if (n_det > 0 && (!det_boxes || !det_scores || !det_labels || !matched || !ignored || !rank_ws))
+    return YMS_ERR_INVALID;
+  if (max_gt_per_image < 0 || (max_gt_per_image > 0 && (!gt_boxes || !gt_labels || !gt_ignore))) return YMS_ERR_INVALID;
+  if (max_gt_per_image > MAP_MAX_GT) return YMS_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(map_match_coco_kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0,
+                     (hipStream_t)stream, det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, P,
+                     (long)n_det, matched, ignored, gt_ignore, rank_ws, rank_ws + n_det);
+  return launch_status();
+}
+
+// host: COCOeval.accumulate over T thresholds, 4 area ranges and maxDets 1 / 10 / 100
+yms_status yms_map_accumulate_coco(int n_det, const float* scores, const int* labels, const int* image,
+                                   const int* rank, const uint16_t* matched, const uint16_t* ignored, int n_thr,
+                                   int n_classes, const int* npig, double* precision, double* recall) {
+  if (n_det < 0 || n_classes <= 0 || n_thr < 1 || n_thr > MAP_MAX_THR || !npig || !precision || !recall)
+    return YMS_ERR_INVALID;
+  if (n_det > 0 && (!scores || !labels || !image || !rank || !matched || !ignored)) return YMS_ERR_INVALID;
+  constexpr int NA = MAP_N_AREA, NM = 3, NR = 101;
+  const int max_dets[NM] = {1, 10, MAP_MAXDET};
+  const long K = n_classes;
+  std::fill(precision, precision + (long)n_thr * NR * K * NA * NM, -1.0);
+  std::fill(recall, recall + (long)n_thr * K * NA * NM, -1.0);
+  std::vector<std::vector<int>> by(n_classes);
+  for (int i = 0; i < n_det; ++i)
+    if (rank[i] >= 0 && rank[i] < MAP_MAXDET && labels[i] >= 0 && labels[i] < n_classes) by[labels[i]].push_back(i);
+  const double eps = std::nextafter(1.0, 2.0) - 1.0;   // np.spacing(1)
+  std::vector<int> sel;
+  std::vector<double> rc, pr;
+  for (int c = 0; c < n_classes; ++c) {
+    std::vector<int>& v = by[c];
+    std::stable_sort(v.begin(), v.end(), [&](int x, int y) {
+      if (scores[x] != scores[y]) return scores[x] > scores[y];
+      if (image[x] != image[y]) return image[x] < image[y];
+      return x < y;
+    });
+    for (int a = 0; a < NA; ++a) {
+      const int np_ = npig[c * NA + a];
+      if (np_ <= 0) continue;
+      for (int mi = 0; mi < NM; ++mi) {
+        sel.clear();
+        for (int i : v)
+          if (rank[i] < max_dets[mi]) sel.push_back(i);
+        const int nd = (int)sel.size();
+        rc.resize(nd);
+        pr.resize(nd);
+        for (int t = 0; t < n_thr; ++t) {
+          double tps = 0.0, fps = 0.0;
+          for (int k = 0; k < nd; ++k) {
+            const long i = (long)a * n_det + sel[k];
+            const bool m = (matched[i] >> t) & 1, ig = (ignored[i] >> t) & 1;
+            if (!ig) { if (m) tps += 1.0; else fps += 1.0; }
+            rc[k] = tps / (double)np_;
+            pr[k] = tps / (fps + tps + eps);
+          }
+          for (int k = nd - 1; k > 0; --k)
+            if (pr[k] > pr[k - 1]) pr[k - 1] = pr[k];
+          recall[(((long)t * K + c) * NA + a) * NM + mi] = nd ? rc[nd - 1] : 0.0;
+          for (int r = 0; r < NR; ++r) {
+            const double thr = (double)r * 0.01;      // np.linspace(0, 1, 101) = arange(101) * 0.01
+            const int pi = (int)(std::lower_bound(rc.begin(), rc.end(), thr) - rc.begin());
+            precision[((((long)t * NR + r) * K + c) * NA + a) * NM + mi] = pi < nd ? pr[pi] : 0.0;
+          }
+        }
+      }
+    }
+  }
   return YMS_OK;
 }
 

@@ -105,6 +105,8 @@ _SIGS = {
     "yms_add_grad2": (_I, [_I, _L, _I, _P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _P]),
     "yms_map_match": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "yms_map_accumulate": (_I, [_I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "yms_map_match_coco": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "yms_map_accumulate_coco": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "yms_det_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "yms_stream_create_cu_subset": (_I, [_I, _I, ctypes.POINTER(ctypes.c_void_p)]),
     "yms_resize_normalize": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _P]),
@@ -153,7 +155,7 @@ _CONV = ("yms_conv_fwd", "yms_conv_dgrad", "yms_conv_dgrad_bnred", "yms_conv_wgr
 _DW = ("yms_dwconv_fwd", "yms_dwconv_dgrad", "yms_dwconv_wgrad")
 # launches whose hipStream_t is the last argument (status-returning entry points ending in a void*)
 # (host-only entry points whose last pointer is a host buffer are listed out explicitly)
-_HOST_ONLY = {"yms_map_accumulate", "yms_pack_job_init"}
+_HOST_ONLY = {"yms_map_accumulate", "yms_map_accumulate_coco", "yms_pack_job_init"}
 _STREAM_LAST = {n for n, (res, args) in _SIGS.items()
                 if res is _I and args and args[-1] is _P and n not in _HOST_ONLY}
 
