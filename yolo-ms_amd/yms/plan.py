@@ -22,6 +22,7 @@ contiguously -- see yms.dist).
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 
 import torch
@@ -43,6 +44,32 @@ def r8(c):
 
 def _al(x):
     return (x + ALIGN - 1) // ALIGN * ALIGN
+
+
+@dataclasses.dataclass(frozen=True)
+class Options:
+    """Everything outside (module, input shapes, dtype, train/eval) that shapes a plan or the way it
+    runs.  Read once per runner.get_plan call (read_options) and part of the plan-cache key: a plan
+    keeps the record it was built under as plan.opts, and a changed switch builds a fresh plan."""
+    stem: bool              # YMS_STEM=0: generic input pack + implicit-GEMM stem (Plan._find_stems)
+    head_fuse: bool         # YMS_HEAD_FUSE=0: two ConvOps per head pair (Builder.sibling_convs)
+    bnred: bool             # YMS_BNRED=0: every BN-backward reduce as its own pass (Plan._find_bnred)
+    wgrad_tail_first: bool  # YMS_WGRAD_FIRST=0: no layer enqueues its weight gradient first (Plan)
+    grad_inplace: bool      # YMS_GRAD_INPLACE=0: always copy the incoming output gradients (runner)
+    wgrad_stream: bool      # YMS_WGRAD_STREAM=0: weight gradients and packs on the main stream (runner)
+    # the library's process-wide direct-conv route (yms_conv_direct_set): it changes
+    # yms_conv_stats_rows and yms_conv_dgrad_bnred_rows, which size the plan's scratch
+    direct: int
+
+
+def read_options():
+    """The only place the plan / runner switches are read from the environment and the library."""
+    def on(name):
+        return os.environ.get(name, "1") != "0"
+
+    return Options(stem=on("YMS_STEM"), head_fuse=on("YMS_HEAD_FUSE"), bnred=on("YMS_BNRED"),
+                   wgrad_tail_first=on("YMS_WGRAD_FIRST"), grad_inplace=on("YMS_GRAD_INPLACE"),
+                   wgrad_stream=on("YMS_WGRAD_STREAM"), direct=L.lib().yms_conv_direct_set(-1))
 
 
 class Buf:
@@ -93,6 +120,11 @@ class Layout:
 
 def _overlap(a, b):
     return a.buf is b.buf and a.off < b.off + b.c and b.off < a.off + a.c
+
+
+def _opt(ptr, v):
+    """(address, channel stride, channel offset) launch arguments of an optional view (ptr: rt.a / rt.g)."""
+    return (ptr(v), v.buf.ld, v.off) if v is not None else (None, 0, 0)
 
 
 def _check_not_in_place(op, y):
@@ -195,12 +227,7 @@ class Rt:
         self.main = None         # backward: torch stream objects (main, weight-gradient side stream)
         self.side = None
         self.gover = None        # backward: buffer idx -> incoming output-gradient tensor used in place
-        # backward: enqueue each layer's weight gradient (side stream) BEFORE its input gradient, so
-        # the side stream's wait on the main stream ends at the BN apply, not after the dgrad
-        # (YMS_WGRAD_FIRST=1: every layer; default "tail": only the layers whose input is the stem's
-        # output, the step's tail, where the main stream has nothing left but the stem's input-side
-        # chain and the side stream's last weight gradient otherwise starts after it; 0: none)
-        self.wgrad_first = os.environ.get("YMS_WGRAD_FIRST", "tail") == "1"
+        self.pgrad = None        # backward: parameter index -> address of its fp32 gradient (None: frozen)
 
     def a(self, v):
         return self.base + v.buf.off
@@ -229,7 +256,197 @@ class Rt:
         return self.side.cuda_stream
 
 
-class ConvOp:
+class Op:
+    """What a plan asks of every op besides fwd / bwd / plan_grads; the default answer is nothing."""
+    flops = 0
+
+    def layout(self, plan, La, Le):
+        pass
+
+    def bn_modules(self):
+        """The Conv blocks (.conv, .bn) whose BatchNorm this op runs."""
+        return ()
+
+    def eval_inputs(self):
+        """The tensors prepare_eval reads: the eval cache is rebuilt when one of them changes."""
+        return [t for m in self.bn_modules()
+                for t in (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var)]
+
+    def pack_specs(self):
+        """(shape, fp32 weight, arena byte offset of the packed copy, for_dgrad[, (second weight,
+        split)]) per training weight pack."""
+        return ()
+
+    def prepare_eval(self, rt):
+        pass
+
+    def z_padding(self, es):
+        """(arena byte offset, bytes) of each training buffer that must start zeroed."""
+        return ()
+
+    def grad_params(self):
+        return []
+
+
+class ConvBase(Op):
+    """The backward that ConvOp, SiblingConvOp, BiasConvOp and DWConvOp share: an input gradient on
+    the main stream and a weight gradient on the side stream, from the same output gradient."""
+    res = None
+    stem_input = None           # plan input index when this conv reads the NCHW input directly
+    tail_wgrad_first = False    # enqueue the weight gradient before the input gradient (Plan)
+    WGRAD = "yms_conv_wgrad"
+
+    def layout_eval(self, plan, Le):
+        self.wp_elems = L.lib().yms_conv_packed_elems(self.sp, 0)
+        self.wpt_elems = L.lib().yms_conv_packed_elems(self.sp, 1)
+        self.e_wp = Le.alloc(self.wp_elems * plan.es)
+
+    def layout_packs(self, plan, La):
+        self.t_wp = La.alloc(self.wp_elems * plan.es)
+        self.t_wpt = La.alloc(self.wpt_elems * plan.es)
+
+    def pack_specs(self):
+        w = self.conv.weight.data_ptr()
+        return [(self.sp, w, self.t_wp, 0), (self.sp, w, self.t_wpt, 1)]
+
+    def prepare_eval(self, rt):
+        L.call("yms_conv_pack_weight", self.sp, self.conv.weight.data_ptr(), rt.eval_base + self.e_wp, 0, rt.st)
+
+    def pack_unless_prepacked(self, rt):
+        if not rt.prepacked:
+            for sp, w, off, for_dgrad in self.pack_specs():
+                L.call("yms_conv_pack_weight", sp, w, rt.base + off, for_dgrad, rt.st)
+
+    def plan_grads(self, T):
+        T.read(self.y)
+        self.acc_res = T.write(self.res) if self.res is not None else 0
+        self.acc_x = T.write(self.x) if self.x.buf.needs_grad else 0
+
+    def dgrad(self, rt, dz, ld, off):
+        x = self.x
+        L.call("yms_conv_dgrad", self.sp, dz, ld, off, rt.base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
+               self.acc_x, rt.st)
+
+    def launch_wgrad(self, rt, dz, ld, off, dw):
+        x = self.x
+        L.call(self.WGRAD, self.sp, rt.a(x), x.buf.ld, x.off, dz, ld, off,
+               rt.gbase + rt.plan.gscratch["wgrad"], self.wg_ws, dw, 0, rt.wst())
+
+    def wgrad(self, rt, dz, ld, off):
+        dw = rt.pgrad(self.pw)
+        if dw is not None:
+            self.launch_wgrad(rt, dz, ld, off, dw)
+
+    def bwd_grads(self, rt, dz, ld, off, wgrad_first=False):
+        """Input gradient, then weight gradient, of the output gradient in channels [off, ..) of dz.
+        wgrad_first enqueues the weight gradient (side stream) BEFORE the input gradient, so the
+        side stream's wait on the main stream ends at the BN apply, not after the dgrad: only for
+        the layers whose input is the stem's output (Plan), the step's tail, where the main stream
+        has nothing left but the stem's input-side chain and the side stream's last weight gradient
+        otherwise starts after it."""
+        if wgrad_first:
+            self.wgrad(rt, dz, ld, off)
+        if self.x.buf.needs_grad:
+            self.dgrad(rt, dz, ld, off)
+        if not wgrad_first:
+            self.wgrad(rt, dz, ld, off)
+
+
+class BNConvBase(ConvBase):
+    """Training path of Conv2d -> BatchNorm2d -> act shared by ConvOp, SiblingConvOp and DWConvOp:
+    the BN state's layout, the forward after the conv launch, and the BN + act backward."""
+    bnred_by = None     # consumer whose input gradient computes this op's BN-backward reduce (ConvOp)
+
+    def parts(self):
+        """(conv block, channel offset of its output in this op's z) per convolution of the forward;
+        each has conv_z, stats_rows and stats_ld."""
+        return ((self, 0),)
+
+    def init_block(self, b, mod, x, y, res, act):
+        self.mod, self.conv, self.x, self.y, self.res, self.act = mod, mod.conv, x, y, res, act
+        self.c = mod.conv.out_channels
+        self.npix = b.n * y.h * y.w
+        self.pw = b.param(mod.conv, "weight")
+        self.pg = b.param(mod.bn, "weight")
+        self.pb = b.param(mod.bn, "bias")
+
+    def layout_bn(self, plan, La):
+        """Training state over this op's c channels -- the pre-BN output z (the backward writes dz over
+        it), the weight packs, scale / shift / (mean, invstd) -- and the scratch the forward's
+        statistics tables (one per part), the BN backward and the weight gradient (wg_ws) need."""
+        c = self.c
+        self.zld = r8(c)
+        self.z = La.alloc(self.npix * self.zld * plan.es)
+        self.layout_packs(plan, La)
+        self.sc = La.alloc(4 * c)
+        self.sh = La.alloc(4 * c)
+        self.mi = La.alloc(8 * c)
+        for m, _ in self.parts():
+            plan.need_scratch("stats", 4 * m.stats_rows * (2 * m.stats_ld + 1))
+        self.bwd_rows = L.lib().yms_bn_bwd_rows(self.npix, c)
+        plan.need_scratch("bwd", 4 * 2 * c * self.bwd_rows)
+        plan.need_scratch("coef", 8 * c)
+        plan.need_scratch("wgrad", self.wg_ws)
+
+    def z_padding(self, es):
+        # z buffers with padding channels (c % 8 != 0, e.g. a head with nc = 3): the convs and the BN
+        # apply (dz written over z) touch only the c real channels, while the input gradient reads
+        # the whole 16-B groups -- padding left as arena garbage (NaN / Inf bit patterns) times the
+        # zero weight rows is NaN, so those z buffers start zeroed and their padding stays zero
+        return [(self.z, self.npix * self.zld * es)] if self.zld != self.c else []
+
+    def fwd_train(self, rt):
+        """Each part's conv into its channels of z, with its batch statistics finalised (running
+        stats updated, scale / shift / (mean, invstd) written) before the next part reuses the
+        statistics scratch; then one affine + act (+ residual) pass z -> y."""
+        base, y = rt.base, self.y
+        stats = base + rt.plan.scratch["stats"]
+        z, sc, sh, mi = base + self.z, base + self.sc, base + self.sh, base + self.mi
+        for m, off in self.parts():
+            m.conv_fwd(rt, z, self.zld, off, None, None, L.ACT_NONE, None, stats)
+            bn = m.mod.bn
+            args = (m.c, stats, m.stats_rows, m.stats_ld, self.npix, bn.weight.data_ptr(), bn.bias.data_ptr(),
+                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                    ctypes.c_float(bn.momentum if bn.momentum is not None else BN_MOMENTUM), ctypes.c_float(bn.eps))
+            if m is self:
+                L.call("yms_bn_finalize", *args, mi, sc, sh, rt.st)
+            else:           # a channel slot of this op's state: mean / invstd rows are self.c apart
+                L.call("yms_bn_finalize_ld", *args, mi + 4 * off, self.c, sc + 4 * off, sh + 4 * off, rt.st)
+        L.call("yms_affine_act", rt.plan.dt, self.npix, self.c, z, self.zld, 0, sc, sh, self.act,
+               *_opt(rt.a, self.res), rt.a(y), y.buf.ld, y.off, rt.st)
+
+    def fwd(self, rt):
+        if rt.training:
+            return self.fwd_train(rt)
+        y, eb = self.y, rt.eval_base      # eval: the folded BN + act (+ residual) in the conv's epilogue
+        self.conv_fwd(rt, rt.a(y), y.buf.ld, y.off, eb + self.e_sc, eb + self.e_sh, self.act, self.res, None)
+
+    def bn_bwd_sums(self, rt, dg, db):
+        """The BN + act backward's per-channel sums: partial rows by the reduce pass -- or already
+        written by the consumer's input gradient (bnred_by), its last writer -- then the finalize:
+        dgamma -> dg, dbeta -> db, the apply pass's coefficients -> the returned address."""
+        base, y, gs = rt.base, self.y, rt.plan.gscratch
+        if self.bnred_by is not None:
+            ws, rows = rt.gbase + gs[self.bnred_key], self.bnred_rows
+        else:
+            ws, rows = rt.gbase + gs["bwd"], self.bwd_rows
+            L.call("yms_bn_act_bwd_reduce", rt.plan.dt, self.npix, self.c, base + self.z, self.zld, 0, rt.g(y),
+                   y.buf.ld, y.off, base + self.sc, base + self.sh, base + self.mi, self.act, ws, rt.st)
+        coef = rt.gbase + gs["coef"]
+        L.call("yms_bn_act_bwd_finalize", self.c, ws, rows, self.npix, dg, db, coef, rt.st)
+        return coef
+
+    def bn_bwd_apply(self, rt, coef):
+        """dz written over z in place (+ the residual's gradient) -> dz's address."""
+        base, y = rt.base, self.y
+        z = base + self.z
+        L.call("yms_bn_act_bwd_apply", rt.plan.dt, self.npix, self.c, z, self.zld, 0, rt.g(y), y.buf.ld, y.off,
+               base + self.sc, base + self.sh, base + self.mi, coef, self.act, z, self.zld, 0,
+               *_opt(rt.g, self.res), self.acc_res, rt.st)
+        return z
+
+
+class ConvOp(BNConvBase):
     """Conv block = Conv2d(bias=False) -> BatchNorm2d -> SiLU/Identity (+ residual),
     components.py:69-77 (residual: Bottleneck :87-93)."""
 
@@ -240,127 +457,75 @@ class ConvOp:
         if conv.stride[0] != conv.stride[1] or conv.padding[0] != conv.padding[1]:
             raise RuntimeError("yms: anisotropic stride/padding unsupported")
         k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        self.mod, self.x, self.y, self.res, self.act = mod, x, y, res, act
+        self.init_block(b, mod, x, y, res, act)
         self.shape = L.ConvShape(b.n, x.h, x.w, conv.in_channels, conv.out_channels, k, s, p,
                                  y.h, y.w, b.dt)
         self.sp = ctypes.pointer(self.shape)
-        self.c = conv.out_channels
-        self.npix = b.n * y.h * y.w
-        self.pw = b.param(conv, "weight")
-        self.pg = b.param(mod.bn, "weight")
-        self.pb = b.param(mod.bn, "bias")
         self.flops = 2 * self.npix * self.c * conv.in_channels * k * k
-        self.stem_input = None   # plan input index when this conv reads the NCHW input directly
-        self.tail_wgrad_first = False   # enqueue the weight gradient before the input gradient (Plan)
         self.bnred_for = None    # producer whose BN-backward reduce this conv's input gradient computes
         self.bnred_by = None     # consumer whose input gradient computes this conv's BN-backward reduce
         self.bnred_key = None    # grad-scratch region of the partial rows of THIS conv's reduce
         self.bnred_wkey = None   # grad-scratch region this conv's input gradient writes (its producer's)
 
     def layout(self, plan, La, Le):
-        es = plan.es
-        self.wp_elems = L.lib().yms_conv_packed_elems(self.sp, 0)
-        self.wpt_elems = L.lib().yms_conv_packed_elems(self.sp, 1)
-        c = self.c
         # eval cache: packed fwd weights + folded scale/shift
-        self.e_wp = Le.alloc(self.wp_elems * es)
-        self.e_sc = Le.alloc(4 * c)
-        self.e_sh = Le.alloc(4 * c)
+        self.layout_eval(plan, Le)
+        self.e_sc = Le.alloc(4 * self.c)
+        self.e_sh = Le.alloc(4 * self.c)
         if plan.training:
-            self.zld = r8(c)
-            self.z = La.alloc(self.npix * self.zld * es)
-            self.t_wp = La.alloc(self.wp_elems * es)
-            self.t_wpt = La.alloc(self.wpt_elems * es)
-            self.sc = La.alloc(4 * c)
-            self.sh = La.alloc(4 * c)
-            self.mi = La.alloc(8 * c)
-            if self.stem_input is not None:
-                self.stats_rows = L.lib().yms_conv_stem_stats_rows(self.sp)
-            else:
-                self.stats_rows = L.lib().yms_conv_stats_rows(self.sp)
+            stem = self.stem_input is not None
+            self.stats_rows = (L.lib().yms_conv_stem_stats_rows if stem else L.lib().yms_conv_stats_rows)(self.sp)
             self.stats_ld = L.lib().yms_conv_stats_ld(self.sp)
-            plan.need_scratch("stats", 4 * self.stats_rows * (2 * self.stats_ld + 1))
-            self.bwd_rows = L.lib().yms_bn_bwd_rows(self.npix, c)
-            plan.need_scratch("bwd", 4 * 2 * c * self.bwd_rows)
-            plan.need_scratch("coef", 8 * c)
             self.wg_ws = L.lib().yms_conv_wgrad_ws_bytes(self.sp)
-            plan.need_scratch("wgrad", self.wg_ws)
-            if self.stem_input is not None:
+            self.layout_bn(plan, La)
+            if stem:
                 # its own scratch: the stem's wgrad runs on the MAIN stream while the side stream
                 # may still be in the previous layers' wgrads, which share the "wgrad" scratch
                 self.wg_ws = L.lib().yms_conv_stem_wgrad_ws_bytes(self.sp)
                 plan.need_scratch("stemwg", self.wg_ws)
 
-    def pack_specs(self):
-        """(shape, fp32 weight, arena byte offset of the packed copy, for_dgrad) per training pack."""
-        w = self.mod.conv.weight.data_ptr()
-        return [(self.sp, w, self.t_wp, 0), (self.sp, w, self.t_wpt, 1)]
+    def bn_modules(self):
+        return (self.mod,)
 
     def prepare_eval(self, rt):
-        m = self.mod
-        L.call("yms_conv_pack_weight", self.sp, m.conv.weight.data_ptr(), rt.eval_base + self.e_wp, 0, rt.st)
-        bn = m.bn
+        super().prepare_eval(rt)
+        self.fold_bn(rt)
+
+    def fold_bn(self, rt):
+        bn = self.mod.bn
         L.call("yms_bn_fold", self.c, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
                bn.running_var.data_ptr(), ctypes.c_float(bn.eps), rt.eval_base + self.e_sc,
                rt.eval_base + self.e_sh, rt.st)
 
     def fwd(self, rt):
-        x, y, r = self.x, self.y, self.res
-        xl, yl = x.buf.ld, y.buf.ld
-        rp = rt.a(r) if r is not None else None
-        rl, ro = (r.buf.ld, r.off) if r is not None else (0, 0)
-        stem = self.stem_input is not None
-        if not rt.training:
-            eb = rt.eval_base
-            if stem:
-                L.call("yms_conv_stem_fwd", self.sp, rt.stem_x[self.stem_input].data_ptr(),
-                       self.mod.conv.weight.data_ptr(), rt.a(y), yl, y.off, eb + self.e_sc, eb + self.e_sh,
-                       self.act, None, 0, rt.st)
-                return
-            L.call("yms_conv_fwd", self.sp, rt.a(x), xl, x.off, eb + self.e_wp, rt.a(y), yl, y.off,
-                   eb + self.e_sc, eb + self.e_sh, self.act, rp, rl, ro, None, rt.st)
-            return
-        m = self.mod
-        base = rt.base
-        if not rt.prepacked:
-            L.call("yms_conv_pack_weight", self.sp, m.conv.weight.data_ptr(), base + self.t_wp, 0, rt.st)
-            L.call("yms_conv_pack_weight", self.sp, m.conv.weight.data_ptr(), base + self.t_wpt, 1, rt.st)
-        stats = base + rt.plan.scratch["stats"]
-        if stem:
-            L.call("yms_conv_stem_fwd", self.sp, rt.stem_x[self.stem_input].data_ptr(), m.conv.weight.data_ptr(),
-                   base + self.z, self.zld, 0, None, None, L.ACT_NONE, stats, self.stats_ld, rt.st)
-        else:
-            L.call("yms_conv_fwd", self.sp, rt.a(x), xl, x.off, base + self.t_wp, base + self.z, self.zld, 0,
-                   None, None, L.ACT_NONE, None, 0, 0, stats, rt.st)
-        bn = m.bn
-        L.call("yms_bn_finalize", self.c, stats, self.stats_rows, self.stats_ld, self.npix, bn.weight.data_ptr(),
-               bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-               ctypes.c_float(bn.momentum if bn.momentum is not None else BN_MOMENTUM),
-               ctypes.c_float(bn.eps), base + self.mi, base + self.sc, base + self.sh, rt.st)
-        L.call("yms_affine_act", rt.plan.dt, self.npix, self.c, base + self.z, self.zld, 0, base + self.sc,
-               base + self.sh, self.act, rp, rl, ro, rt.a(y), yl, y.off, rt.st)
+        if rt.training:
+            self.pack_unless_prepacked(rt)
+        super().fwd(rt)
 
-    def plan_grads(self, T):
-        T.read(self.y)
-        self.acc_res = T.write(self.res) if self.res is not None else 0
-        self.acc_x = T.write(self.x) if self.x.buf.needs_grad else 0
+    def conv_fwd(self, rt, out, ld, off, sc, sh, act, res, stats):
+        """The conv into channels [off, off + c) of out, with scale / shift, act and residual in the
+        epilogue (eval) or the batch-statistics table into stats (training: the pre-BN output)."""
+        x = self.x
+        if self.stem_input is not None:
+            L.call("yms_conv_stem_fwd", self.sp, rt.stem_x[self.stem_input].data_ptr(), self.conv.weight.data_ptr(),
+                   out, ld, off, sc, sh, act, stats, self.stats_ld if stats else 0, rt.st)
+        else:
+            wp = rt.base + self.t_wp if rt.training else rt.eval_base + self.e_wp
+            L.call("yms_conv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, wp, out, ld, off, sc, sh, act,
+                   *_opt(rt.a, res), stats, rt.st)
+
+    def dgrad(self, rt, dz, ld, off):
+        q = self.bnred_for
+        if q is None:
+            return super().dgrad(rt, dz, ld, off)
+        # + the producer's BN-backward reduce in the epilogue (dx = the producer's final gy)
+        x, base = self.x, rt.base
+        L.call("yms_conv_dgrad_bnred", self.sp, dz, ld, off, base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
+               self.acc_x, base + q.z, q.zld, 0, base + q.sc, base + q.sh, base + q.mi, q.act,
+               rt.gbase + rt.plan.gscratch[self.bnred_wkey], rt.st)
 
     def bwd(self, rt):
-        x, y, r = self.x, self.y, self.res
-        base, dt, c = rt.base, rt.plan.dt, self.c
-        gy, gyl, gyo = rt.g(y), y.buf.ld, y.off
-        ws = rt.gbase + rt.plan.gscratch["bwd"]
-        coef = rt.gbase + rt.plan.gscratch["coef"]
-        z = base + self.z
-        if self.bnred_by is not None:
-            # the consumer's input gradient (its last writer) already summed the partial rows
-            L.call("yms_bn_act_bwd_finalize", c, rt.gbase + rt.plan.gscratch[self.bnred_key], self.bnred_rows,
-                   self.npix, rt.pgrad(self.pg), rt.pgrad(self.pb), coef, rt.st)
-        else:
-            L.call("yms_bn_act_bwd_reduce", dt, self.npix, c, z, self.zld, 0, gy, gyl, gyo, base + self.sc,
-                   base + self.sh, base + self.mi, self.act, ws, rt.st)
-            L.call("yms_bn_act_bwd_finalize", c, ws, self.bwd_rows, self.npix,
-                   rt.pgrad(self.pg), rt.pgrad(self.pb), coef, rt.st)
+        coef = self.bn_bwd_sums(rt, rt.pgrad(self.pg), rt.pgrad(self.pb))
         if self.stem_input is not None:
             # the stem's input needs no gradient: the apply pass is fused into the weight
             # gradient, which reads gy, z and the NCHW input.
@@ -369,48 +534,19 @@ class ConvOp:
             # weight gradients -- the two then overlap instead of queueing (step tail 0.53 ms).
             dw = rt.pgrad(self.pw)
             if dw is not None:
-                st = rt.st
-                xs = rt.stem_x[self.stem_input]
-                L.call("yms_conv_stem_wgrad", self.sp, xs.data_ptr(), gy, gyl, gyo, z, self.zld, 0, base + self.sc,
-                       base + self.sh, base + self.mi, coef, self.act,
-                       rt.gbase + rt.plan.gscratch["stemwg"],
-                       self.wg_ws, dw, 0, st)
+                base, y = rt.base, self.y
+                L.call("yms_conv_stem_wgrad", self.sp, rt.stem_x[self.stem_input].data_ptr(), rt.g(y), y.buf.ld,
+                       y.off, base + self.z, self.zld, 0, base + self.sc, base + self.sh, base + self.mi, coef,
+                       self.act, rt.gbase + rt.plan.gscratch["stemwg"], self.wg_ws, dw, 0, rt.st)
             return
-        gres = rt.g(r) if r is not None else None
-        gro = (r.buf.ld, r.off) if r is not None else (0, 0)
-        dz = z                   # dz overwrites z in place
-        L.call("yms_bn_act_bwd_apply", dt, self.npix, c, z, self.zld, 0, gy, gyl, gyo, base + self.sc,
-               base + self.sh, base + self.mi, coef, self.act, dz, self.zld, 0, gres, gro[0], gro[1], self.acc_res,
-               rt.st)
-        def dgrad():
-            if not x.buf.needs_grad:
-                return
-            q = self.bnred_for
-            if q is not None:
-                # + the producer's BN-backward reduce in the epilogue (dx = the producer's final gy)
-                L.call("yms_conv_dgrad_bnred", self.sp, dz, self.zld, 0, base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
-                       self.acc_x, base + q.z, q.zld, 0, base + q.sc, base + q.sh, base + q.mi, q.act,
-                       rt.gbase + rt.plan.gscratch[self.bnred_wkey], rt.st)
-            else:
-                L.call("yms_conv_dgrad", self.sp, dz, self.zld, 0, base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
-                       self.acc_x, rt.st)
-
-        dw = rt.pgrad(self.pw)
-        first = rt.wgrad_first or self.tail_wgrad_first
-        if not first:
-            dgrad()
-        if dw is not None:
-            wsz = self.wg_ws
-            L.call("yms_conv_wgrad", self.sp, rt.a(x), x.buf.ld, x.off, dz, self.zld, 0,
-                   rt.gbase + rt.plan.gscratch["wgrad"], wsz, dw, 0, rt.wst())
-        if first:
-            dgrad()
+        dz = self.bn_bwd_apply(rt, coef)
+        self.bwd_grads(rt, dz, self.zld, 0, self.tail_wgrad_first)
 
     def grad_params(self):
         return [self.pb, self.pg, self.pw]
 
 
-class SiblingConvOp:
+class SiblingConvOp(BNConvBase):
     """Two Conv blocks (Conv2d -> BN -> act, components.py:69-77) that read the SAME input view --
     the head's box[i][0] and cls[i][0] (yolov8_head.py:84-85, 99-100: Conv(c_i, 4*ch) and
     Conv(c_i, nc), both 3x3 of x_i) -- with their outputs as the two channel slots of one buffer
@@ -437,7 +573,9 @@ class SiblingConvOp:
         self.sp = ctypes.pointer(self.shape)
         self.npix = m0.npix
         self.flops = sum(m.flops for m in self.members)
-        self.stem_input = None
+
+    def parts(self):
+        return zip(self.members, self.offs)
 
     def layout(self, plan, La, Le):
         es = plan.es
@@ -448,33 +586,24 @@ class SiblingConvOp:
             m.e_sh = Le.alloc(4 * m.c)
         if not plan.training:
             return
-        c = self.c
-        self.zld = r8(c)
-        self.z = La.alloc(self.npix * self.zld * es)
         for m in self.members:
-            m.t_wp = La.alloc(m.wp_elems * es)
             m.stats_rows = L.lib().yms_conv_stats_rows(m.sp)
             m.stats_ld = L.lib().yms_conv_stats_ld(m.sp)
-            plan.need_scratch("stats", 4 * m.stats_rows * (2 * m.stats_ld + 1))
-        self.wpt_elems = L.lib().yms_conv_packed_elems(self.sp, 1)
-        self.t_wpt = La.alloc(self.wpt_elems * es)
-        self.sc = La.alloc(4 * c)
-        self.sh = La.alloc(4 * c)
-        self.mi = La.alloc(8 * c)
-        self.bwd_rows = L.lib().yms_bn_bwd_rows(self.npix, c)
-        plan.need_scratch("bwd", 4 * 2 * c * self.bwd_rows)
-        plan.need_scratch("coef", 8 * c)
-        # the fallback when the members' parameter gradients are not adjacent (some frozen):
-        # dgamma / dbeta into scratch, then per member
-        plan.need_scratch("sib", 8 * c)
-        self.wg_ws = L.lib().yms_conv_wgrad_ws_bytes(self.sp)
-        plan.need_scratch("wgrad", self.wg_ws)
-        for m in self.members:
+            # the fallback when the members' weight gradients are not adjacent (some frozen): per member
             m.wg_ws = L.lib().yms_conv_wgrad_ws_bytes(m.sp)
             plan.need_scratch("wgrad", m.wg_ws)
+        self.wpt_elems = L.lib().yms_conv_packed_elems(self.sp, 1)
+        self.wg_ws = L.lib().yms_conv_wgrad_ws_bytes(self.sp)
+        self.layout_bn(plan, La)
+        # the same fallback for dgamma / dbeta: into scratch, then copied per member
+        plan.need_scratch("sib", 8 * self.c)
+
+    def layout_packs(self, plan, La):
+        for m in self.members:
+            m.t_wp = La.alloc(m.wp_elems * plan.es)
+        self.t_wpt = La.alloc(self.wpt_elems * plan.es)
 
     def pack_specs(self):
-        """(shape, fp32 weight, arena offset, for_dgrad[, (second weight, split)]) per pack."""
         specs = [(m.sp, m.mod.conv.weight.data_ptr(), m.t_wp, 0) for m in self.members]
         a, bb = self.members
         specs.append((self.sp, a.mod.conv.weight.data_ptr(), self.t_wpt, 1,
@@ -495,24 +624,7 @@ class SiblingConvOp:
             return
         if not rt.prepacked:
             raise RuntimeError("yms: sibling convs need the batched pack (Plan.prepack)")
-        x, y = self.x, self.y
-        base = rt.base
-        stats = base + rt.plan.scratch["stats"]
-        for m, off in zip(self.members, self.offs):
-            L.call("yms_conv_fwd", m.sp, rt.a(x), x.buf.ld, x.off, base + m.t_wp, base + self.z, self.zld, off,
-                   None, None, L.ACT_NONE, None, 0, 0, stats, rt.st)
-            bn = m.mod.bn
-            L.call("yms_bn_finalize_ld", m.c, stats, m.stats_rows, m.stats_ld, self.npix, bn.weight.data_ptr(),
-                   bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                   ctypes.c_float(bn.momentum if bn.momentum is not None else BN_MOMENTUM),
-                   ctypes.c_float(bn.eps), base + self.mi + 4 * off, self.c, base + self.sc + 4 * off,
-                   base + self.sh + 4 * off, rt.st)
-        L.call("yms_affine_act", rt.plan.dt, self.npix, self.c, base + self.z, self.zld, 0, base + self.sc,
-               base + self.sh, self.act, None, 0, 0, rt.a(y), y.buf.ld, y.off, rt.st)
-
-    def plan_grads(self, T):
-        T.read(self.y)
-        self.acc_x = T.write(self.x) if self.x.buf.needs_grad else 0
+        self.fwd_train(rt)
 
     def _adjacent(self, rt, attr):
         ps = [rt.pgrad(getattr(m, attr)) for m in self.members]
@@ -525,47 +637,28 @@ class SiblingConvOp:
         return ps[0]
 
     def bwd(self, rt):
-        x, y = self.x, self.y
-        base, dt, c = rt.base, rt.plan.dt, self.c
-        gy, gyl, gyo = rt.g(y), y.buf.ld, y.off
-        ws = rt.gbase + rt.plan.gscratch["bwd"]
-        coef = rt.gbase + rt.plan.gscratch["coef"]
-        z = base + self.z
-        L.call("yms_bn_act_bwd_reduce", dt, self.npix, c, z, self.zld, 0, gy, gyl, gyo, base + self.sc,
-               base + self.sh, base + self.mi, self.act, ws, rt.st)
+        c = self.c
         dg, db = self._adjacent(rt, "pg"), self._adjacent(rt, "pb")
         if dg is not None and db is not None:
-            L.call("yms_bn_act_bwd_finalize", c, ws, self.bwd_rows, self.npix, dg, db, coef, rt.st)
+            coef = self.bn_bwd_sums(rt, dg, db)
         else:
             tmp = rt.gbase + rt.plan.gscratch["sib"]
-            L.call("yms_bn_act_bwd_finalize", c, ws, self.bwd_rows, self.npix, tmp, tmp + 4 * c, coef, rt.st)
-            for m, off in zip(self.members, self.offs):
+            coef = self.bn_bwd_sums(rt, tmp, tmp + 4 * c)
+            for m, off in self.parts():
                 for src, pi in ((tmp, m.pg), (tmp + 4 * c, m.pb)):
                     d = rt.pgrad(pi)
                     if d is not None:
                         L.call("yms_copy", d, src + 4 * off, 4 * m.c, rt.st)
-        dz = z                   # dz overwrites z in place
-        L.call("yms_bn_act_bwd_apply", dt, self.npix, c, z, self.zld, 0, gy, gyl, gyo, base + self.sc,
-               base + self.sh, base + self.mi, coef, self.act, dz, self.zld, 0, None, 0, 0, 0, rt.st)
-        def dgrad():
-            if x.buf.needs_grad:
-                L.call("yms_conv_dgrad", self.sp, dz, self.zld, 0, base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
-                       self.acc_x, rt.st)
+        dz = self.bn_bwd_apply(rt, coef)
+        self.bwd_grads(rt, dz, self.zld, 0)
 
-        if not rt.wgrad_first:
-            dgrad()
+    def wgrad(self, rt, dz, ld, off):
         dw = self._adjacent(rt, "pw")
         if dw is not None:
-            L.call("yms_conv_wgrad", self.sp, rt.a(x), x.buf.ld, x.off, dz, self.zld, 0,
-                   rt.gbase + rt.plan.gscratch["wgrad"], self.wg_ws, dw, 0, rt.wst())
+            self.launch_wgrad(rt, dz, ld, off, dw)
         else:
-            for m, off in zip(self.members, self.offs):
-                d = rt.pgrad(m.pw)
-                if d is not None:
-                    L.call("yms_conv_wgrad", m.sp, rt.a(x), x.buf.ld, x.off, dz, self.zld, off,
-                           rt.gbase + rt.plan.gscratch["wgrad"], m.wg_ws, d, 0, rt.wst())
-        if rt.wgrad_first:
-            dgrad()
+            for m, moff in self.parts():
+                m.wgrad(rt, dz, ld, off + moff)
 
     def grad_params(self):
         # member-major within each kind: the flat arena then holds [dbeta_a | dbeta_b],
@@ -573,7 +666,7 @@ class SiblingConvOp:
         return [m.pb for m in self.members] + [m.pg for m in self.members] + [m.pw for m in self.members]
 
 
-class BiasConvOp:
+class BiasConvOp(ConvBase):
     """Plain nn.Conv2d with bias (the head's final 1x1 layers, yolov8_head.py:86-109)."""
 
     def __init__(self, b, conv, x, y):
@@ -588,65 +681,37 @@ class BiasConvOp:
         self.pw = b.param(conv, "weight")
         self.pbias = b.param(conv, "bias")
         self.flops = 2 * self.npix * self.c * conv.in_channels * k * k
-        self.stem_input = None   # plan input index when this conv reads the NCHW input directly
-        self.tail_wgrad_first = False   # enqueue the weight gradient before the input gradient (Plan)
 
     def layout(self, plan, La, Le):
-        es = plan.es
-        self.wp_elems = L.lib().yms_conv_packed_elems(self.sp, 0)
-        self.wpt_elems = L.lib().yms_conv_packed_elems(self.sp, 1)
-        self.e_wp = Le.alloc(self.wp_elems * es)
+        self.layout_eval(plan, Le)
         if plan.training:
-            self.t_wp = La.alloc(self.wp_elems * es)
-            self.t_wpt = La.alloc(self.wpt_elems * es)
+            self.layout_packs(plan, La)
             plan.need_scratch("bwd", 4 * 2 * self.c * L.lib().yms_bn_bwd_rows(self.npix, self.c))
             self.wg_ws = L.lib().yms_conv_wgrad_ws_bytes(self.sp)
             plan.need_scratch("wgrad", self.wg_ws)
             self.cnt = plan.counter()
 
-    def prepare_eval(self, rt):
-        L.call("yms_conv_pack_weight", self.sp, self.conv.weight.data_ptr(), rt.eval_base + self.e_wp, 0, rt.st)
-
-    def pack_specs(self):
-        w = self.conv.weight.data_ptr()
-        return [(self.sp, w, self.t_wp, 0), (self.sp, w, self.t_wpt, 1)]
+    def eval_inputs(self):
+        return [self.conv.weight]
 
     def fwd(self, rt):
         x, y = self.x, self.y
         if rt.training:
             wp = rt.base + self.t_wp
-            if not rt.prepacked:
-                L.call("yms_conv_pack_weight", self.sp, self.conv.weight.data_ptr(), wp, 0, rt.st)
-                L.call("yms_conv_pack_weight", self.sp, self.conv.weight.data_ptr(), rt.base + self.t_wpt, 1, rt.st)
+            self.pack_unless_prepacked(rt)
         else:
             wp = rt.eval_base + self.e_wp
         L.call("yms_conv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, wp, rt.a(y), y.buf.ld, y.off,
                None, self.conv.bias.data_ptr(), L.ACT_NONE, None, 0, 0, None, rt.st)
 
-    def plan_grads(self, T):
-        T.read(self.y)
-        self.acc_x = T.write(self.x) if self.x.buf.needs_grad else 0
-
     def bwd(self, rt):
-        x, y = self.x, self.y
+        y = self.y
         gy, gyl, gyo = rt.g(y), y.buf.ld, y.off
         db = rt.pgrad(self.pbias)
         if db is not None:
             L.call("yms_bias_bwd", rt.plan.dt, self.npix, self.c, gy, gyl, gyo,
                    rt.gbase + rt.plan.gscratch["bwd"], rt.cnt(self.cnt), db, rt.st)
-        def dgrad():
-            if x.buf.needs_grad:
-                L.call("yms_conv_dgrad", self.sp, gy, gyl, gyo, rt.base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
-                       self.acc_x, rt.st)
-
-        if not rt.wgrad_first:
-            dgrad()
-        dw = rt.pgrad(self.pw)
-        if dw is not None:
-            L.call("yms_conv_wgrad", self.sp, rt.a(x), x.buf.ld, x.off, gy, gyl, gyo,
-                   rt.gbase + rt.plan.gscratch["wgrad"], self.wg_ws, dw, 0, rt.wst())
-        if rt.wgrad_first:
-            dgrad()
+        self.bwd_grads(rt, gy, gyl, gyo)
 
     def grad_params(self):
         return [self.pbias, self.pw]
@@ -655,7 +720,9 @@ class BiasConvOp:
 class DWConvOp(ConvOp):
     """Depthwise Conv block (YOLO-MS IB_k mid conv, yolov8/model/yolo_ms.py): Conv2d(groups=C,
     bias=False, k x k, stride 1, pad k//2) -> BatchNorm2d -> SiLU, on the dwconv kernels.  BN
-    forward/backward are the ConvOp path; weights are read unpacked (fp32 [C][k][k])."""
+    forward/backward are the ConvOp path (inherited: only the conv launches and the layout differ);
+    weights are read unpacked (fp32 [C][k][k])."""
+    WGRAD = "yms_dwconv_wgrad"
 
     def __init__(self, b, mod, x, y, act):
         conv = mod.conv
@@ -666,93 +733,45 @@ class DWConvOp(ConvOp):
                 and conv.dilation == (1, 1)):
             raise RuntimeError("yms: grouped convolutions are supported as depthwise k x k (k = 3/5/7/9), "
                                "stride 1, pad k//2")
-        self.mod, self.x, self.y, self.res, self.act = mod, x, y, None, act
+        self.init_block(b, mod, x, y, None, act)
         self.dshape = L.DwShape(b.n, x.h, x.w, c, k, b.dt)
         self.sp = ctypes.pointer(self.dshape)
-        self.c = c
-        self.npix = b.n * y.h * y.w
-        self.pw = b.param(conv, "weight")
-        self.pg = b.param(mod.bn, "weight")
-        self.pb = b.param(mod.bn, "bias")
-        self.flops = 0          # not an MFMA contraction: excluded from the conv roofline
+        self.flops = 0         # not an MFMA contraction: excluded from the conv roofline
         self.dw_flops = 2 * self.npix * c * k * k
-        self.stem_input = None
         self.bnred_for = self.bnred_by = self.bnred_key = self.bnred_wkey = None   # (ConvOp's fused-reduce links: unused)
 
     def layout(self, plan, La, Le):
-        es, c = plan.es, self.c
-        self.e_sc = Le.alloc(4 * c)
-        self.e_sh = Le.alloc(4 * c)
+        self.e_sc = Le.alloc(4 * self.c)
+        self.e_sh = Le.alloc(4 * self.c)
         if plan.training:
-            self.zld = r8(c)
-            self.z = La.alloc(self.npix * self.zld * es)
-            self.sc = La.alloc(4 * c)
-            self.sh = La.alloc(4 * c)
-            self.mi = La.alloc(8 * c)
             self.stats_rows = L.lib().yms_dwconv_stats_rows(self.sp)
-            self.stats_ld = r8(c)
-            plan.need_scratch("stats", 4 * self.stats_rows * (2 * self.stats_ld + 1))
-            plan.need_scratch("bwd", 4 * 2 * c * L.lib().yms_bn_bwd_rows(self.npix, c))
-            plan.need_scratch("coef", 8 * c)
+            self.stats_ld = r8(self.c)
             # sized once here and passed as-is at backward time: the C side reads its tiling knobs
             # on every call, so a recomputed size could outgrow the region reserved here
             self.wg_ws = L.lib().yms_dwconv_wgrad_ws_bytes(self.sp)
-            plan.need_scratch("wgrad", self.wg_ws)
+            self.layout_bn(plan, La)
+
+    def layout_packs(self, plan, La):
+        pass
 
     def pack_specs(self):
-        return []
+        return ()
 
     def prepare_eval(self, rt):
-        bn = self.mod.bn
-        L.call("yms_bn_fold", self.c, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-               bn.running_var.data_ptr(), ctypes.c_float(bn.eps), rt.eval_base + self.e_sc,
-               rt.eval_base + self.e_sh, rt.st)
+        self.fold_bn(rt)
 
-    def fwd(self, rt):
-        x, y = self.x, self.y
-        w = self.mod.conv.weight.data_ptr()
-        if not rt.training:
-            eb = rt.eval_base
-            L.call("yms_dwconv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, w, rt.a(y), y.buf.ld, y.off, eb + self.e_sc,
-                   eb + self.e_sh, self.act, None, 0, rt.st)
-            return
-        base = rt.base
-        stats = base + rt.plan.scratch["stats"]
-        L.call("yms_dwconv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, w, base + self.z, self.zld, 0, None, None,
-               L.ACT_NONE, stats, self.stats_ld, rt.st)
-        bn = self.mod.bn
-        L.call("yms_bn_finalize", self.c, stats, self.stats_rows, self.stats_ld, self.npix, bn.weight.data_ptr(),
-               bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-               ctypes.c_float(bn.momentum if bn.momentum is not None else BN_MOMENTUM),
-               ctypes.c_float(bn.eps), base + self.mi, base + self.sc, base + self.sh, rt.st)
-        L.call("yms_affine_act", rt.plan.dt, self.npix, self.c, base + self.z, self.zld, 0, base + self.sc,
-               base + self.sh, self.act, None, 0, 0, rt.a(y), y.buf.ld, y.off, rt.st)
+    def conv_fwd(self, rt, out, ld, off, sc, sh, act, res, stats):
+        x = self.x
+        L.call("yms_dwconv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, self.conv.weight.data_ptr(), out, ld, off,
+               sc, sh, act, stats, self.stats_ld if stats else 0, rt.st)
 
-    def bwd(self, rt):
-        x, y = self.x, self.y
-        base, dt, c = rt.base, rt.plan.dt, self.c
-        z = base + self.z
-        ws = rt.gbase + rt.plan.gscratch["bwd"]
-        coef = rt.gbase + rt.plan.gscratch["coef"]
-        L.call("yms_bn_act_bwd_reduce", dt, self.npix, c, z, self.zld, 0, rt.g(y), y.buf.ld, y.off, base + self.sc,
-               base + self.sh, base + self.mi, self.act, ws, rt.st)
-        L.call("yms_bn_act_bwd_finalize", c, ws, L.lib().yms_bn_bwd_rows(self.npix, c), self.npix,
-               rt.pgrad(self.pg), rt.pgrad(self.pb), coef, rt.st)
-        L.call("yms_bn_act_bwd_apply", dt, self.npix, c, z, self.zld, 0, rt.g(y), y.buf.ld, y.off, base + self.sc,
-               base + self.sh, base + self.mi, coef, self.act, z, self.zld, 0, None, 0, 0, 0, rt.st)
-        w = self.mod.conv.weight.data_ptr()
-        if x.buf.needs_grad and not rt.wgrad_first:
-            L.call("yms_dwconv_dgrad", self.sp, z, self.zld, 0, w, rt.g(x), x.buf.ld, x.off, self.acc_x, rt.st)
-        dw = rt.pgrad(self.pw)
-        if dw is not None:
-            wsz = self.wg_ws
-            L.call("yms_dwconv_wgrad", self.sp, rt.a(x), x.buf.ld, x.off, z, self.zld, 0,
-                   rt.gbase + rt.plan.gscratch["wgrad"], wsz, dw, 0, rt.wst())
-        if x.buf.needs_grad and rt.wgrad_first:
-            L.call("yms_dwconv_dgrad", self.sp, z, self.zld, 0, w, rt.g(x), x.buf.ld, x.off, self.acc_x, rt.st)
+    def dgrad(self, rt, dz, ld, off):
+        x = self.x
+        L.call("yms_dwconv_dgrad", self.sp, dz, ld, off, self.conv.weight.data_ptr(), rt.g(x), x.buf.ld, x.off,
+               self.acc_x, rt.st)
 
 
-class AddOp:
+class AddOp(Op):
     """y = a + b (b None: y = a) over channel views: the MS-Block branch sums X_i + Y_{i-1} and
     the Y_1 = X_1 placement.  Backward routes dy into both addends (store or accumulate)."""
 
@@ -760,17 +779,11 @@ class AddOp:
         self.a, self.b, self.y = a, bb, y
         self.npix = b.n * y.h * y.w
         self.c = y.c
-        self.flops = 0
-
-    def layout(self, plan, La, Le):
-        pass
 
     def fwd(self, rt):
-        a, b, y = self.a, self.b, self.y
-        bp = rt.a(b) if b is not None else None
-        bl, bo = (b.buf.ld, b.off) if b is not None else (0, 0)
-        L.call("yms_add_views", rt.plan.dt, self.npix, self.c, rt.a(a), a.buf.ld, a.off, bp, bl, bo, rt.a(y),
-               y.buf.ld, y.off, 0, rt.st)
+        a, y = self.a, self.y
+        L.call("yms_add_views", rt.plan.dt, self.npix, self.c, rt.a(a), a.buf.ld, a.off, *_opt(rt.a, self.b),
+               rt.a(y), y.buf.ld, y.off, 0, rt.st)
 
     def plan_grads(self, T):
         T.read(self.y)
@@ -789,19 +802,12 @@ class AddOp:
             L.call("yms_add_views", rt.plan.dt, self.npix, self.c, rt.g(y), y.buf.ld, y.off, None, 0, 0, rt.g(v),
                    v.buf.ld, v.off, acc, rt.st)
 
-    def grad_params(self):
-        return []
 
-
-class UpsampleOp:
+class UpsampleOp(Op):
     """nearest x2, components.py:153-160."""
 
     def __init__(self, b, x, y):
         self.x, self.y, self.n = x, y, b.n
-        self.flops = 0
-
-    def layout(self, plan, La, Le):
-        pass
 
     def fwd(self, rt):
         x, y = self.x, self.y
@@ -819,16 +825,12 @@ class UpsampleOp:
         L.call("yms_upsample2x_bwd", rt.plan.dt, self.n, x.h, x.w, x.c, rt.g(y), y.buf.ld, y.off,
                rt.g(x), x.buf.ld, x.off, self.acc_x, rt.st)
 
-    def grad_params(self):
-        return []
 
-
-class SppfPoolOp:
+class SppfPoolOp(Op):
     """The three chained MaxPool2d(5,1,2) of SPPF (components.py:136-146) over a 4-slot buffer."""
 
     def __init__(self, b, v4, c):
         self.v, self.c, self.n = v4, c, b.n
-        self.flops = 0
 
     def layout(self, plan, La, Le):
         if plan.training:
@@ -846,15 +848,13 @@ class SppfPoolOp:
         L.call("yms_sppf_pool_bwd", rt.plan.dt, self.n, v.h, v.w, self.c, rt.a(v), v.buf.ld, v.off,
                rt.g(v), v.buf.ld, v.off, rt.gbase + rt.plan.gscratch["sppf"], rt.st)
 
-    def grad_params(self):
-        return []
-
 
 class Builder:
     """Collects buffers, ops and parameter references while modules ``emit``."""
 
-    def __init__(self, n, dt, training):
+    def __init__(self, n, dt, training, opts=None):
         self.n, self.dt, self.training = n, dt, training
+        self.opts = opts if opts is not None else read_options()
         self.es = 4 if dt == L.F32 else 2
         self.bufs = []
         self.ops = []
@@ -899,7 +899,7 @@ class Builder:
         ks = {(m.conv.kernel_size, m.conv.stride, m.conv.padding, m.conv.groups, m.conv.dilation,
                isinstance(m.activation, torch.nn.SiLU)) for m in mods}
         fuse = (len(mods) == 2 and len(ks) == 1 and mods[0].conv.groups == 1 and mods[0].conv.out_channels % 8 == 0
-                and os.environ.get("YMS_HEAD_FUSE", "1") != "0")
+                and self.opts.head_fuse)
         if not fuse:
             return [m.emit(self, x) for m in mods]
         conv = mods[0].conv
@@ -943,10 +943,16 @@ class Plan:
         self.n, self.dt, self.training, self.es = b.n, b.dt, b.training, b.es
         self.bufs, self.ops, self.param_refs = b.bufs, b.ops, b.param_refs
         self.inputs, self.outputs, self.kind = inputs, outputs, kind
+        self.opts = b.opts
         self.scratch_req = {}
         self.n_counters = 0
+        # per-plan caches of the runner
+        self._pack_tables = {}      # parameter set -> the batched pack's device job table (pack_table)
+        self._pg_layouts = {}       # requires_grad pattern -> flat parameter-gradient arena layout
+        self._infer_arenas = {}     # (stream, host thread) -> a decode plan's internal arena
+        self._nbt = None            # the BatchNorm num_batches_tracked tensors a training step bumps
         self.stem_inputs = self._find_stems()
-        if self.training and os.environ.get("YMS_WGRAD_FIRST", "tail") == "tail":
+        if self.training and self.opts.wgrad_tail_first:
             stem_out = {op.y.buf.idx for op in self.stem_inputs.values()}
             for op in self.ops:
                 if type(op) is ConvOp and op.x.buf.idx in stem_out:
@@ -978,16 +984,9 @@ class Plan:
         self.garena_bytes = Lg.size
         self.eval_bytes = Le.size
         self.zero_ranges = [(bf.off, bf.npix * bf.ld * self.es) for bf in self.bufs if bf.zero]
-        # training z buffers with padding channels (c % 8 != 0, e.g. a head with nc = 3): the convs and
-        # the BN apply (dz written over z) touch only the c real channels, while the input gradient
-        # reads the whole 16-B groups -- padding left as arena garbage (NaN / Inf bit patterns) times
-        # the zero weight rows is NaN, so those z buffers start zeroed and their padding stays zero
         if self.training:
             for op in self.ops:
-                zld, z = getattr(op, "zld", None), getattr(op, "z", None)
-                if zld is not None and z is not None and zld != op.c:
-                    self.zero_ranges.append((z, op.npix * zld * self.es))
-        if self.training:
+                self.zero_ranges.extend(op.z_padding(self.es))
             T = GradTracker()
             self.seed_acc = [T.write(v) for v in self.outputs]
             T.writes = set()
@@ -1021,7 +1020,7 @@ class Plan:
         itself (yms_conv_stem_fwd, and yms_conv_stem_wgrad with the BN backward apply fused in),
         so the NHWC input pack goes.  YMS_STEM=0 keeps the generic pack + implicit-GEMM path."""
         out = {}
-        if self.dt == L.F32 or os.environ.get("YMS_STEM", "1") == "0":
+        if self.dt == L.F32 or not self.opts.stem:
             return out
         for i, v in enumerate(self.inputs):
             readers = [op for op in self.ops
@@ -1044,7 +1043,7 @@ class Plan:
         (yms_conv_dgrad_bnred): P's separate reduce pass (z and gy read once more) goes, and P's
         finalize reads the partial rows from a grad-scratch region of their own.  YMS_BNRED=0 keeps
         the separate reduce (A/B)."""
-        if not self.training or self.dt == L.F32 or os.environ.get("YMS_BNRED", "1") == "0":
+        if not self.training or self.dt == L.F32 or not self.opts.bnred:
             return
 
         def views(op):
@@ -1094,15 +1093,7 @@ class Plan:
     # ------------------------------------------------------------------------------------
     def ensure_eval_cache(self, device, stream):
         """(Re)pack weights and fold BN when any parameter / buffer changed."""
-        sig = []
-        for op in self.ops:
-            if isinstance(op, (ConvOp, SiblingConvOp)):
-                for m in (op.bn_modules() if isinstance(op, SiblingConvOp) else (op.mod,)):
-                    for t in (m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var):
-                        sig.append((t.data_ptr(), t._version))
-            elif isinstance(op, BiasConvOp):
-                sig.append((op.conv.weight.data_ptr(), op.conv.weight._version))
-        sig = tuple(sig)
+        sig = tuple((t.data_ptr(), t._version) for op in self.ops for t in op.eval_inputs())
         if self._eval_arena is None or self._eval_arena.device != device:
             self._eval_arena = torch.empty(max(self.eval_bytes, 1), dtype=torch.uint8, device=device)
             self._eval_sig = None
@@ -1110,17 +1101,16 @@ class Plan:
             rt = Rt(self, None, stream, False)
             rt.eval_base = self._eval_arena.data_ptr()
             for op in self.ops:
-                if hasattr(op, "prepare_eval"):
-                    op.prepare_eval(rt)
+                op.prepare_eval(rt)
             self._eval_sig = sig
         return self._eval_arena.data_ptr()
 
     def pack_table(self):
         """The batched pack's device job table (built and uploaded on the CURRENT stream on a
         cache miss: call it before handing prepack to another stream)."""
-        specs = [sp for op in self.ops if hasattr(op, "pack_specs") for sp in op.pack_specs()]
+        specs = [sp for op in self.ops for sp in op.pack_specs()]
         key = tuple((sp[1], sp[2], sp[4] if len(sp) > 4 else None) for sp in specs)
-        cache = self.__dict__.setdefault("_pack_tables", {})
+        cache = self._pack_tables
         ent = cache.get(key)
         if ent is None:
             jobs, singles = [], []

@@ -9,14 +9,13 @@ ATen-conv fallback: CPU tensors or a missing libyms.so raise RuntimeError.
 """
 from __future__ import annotations
 
-import os
-
+import ctypes
 import threading
 
 import torch
 
 from . import _lib as L
-from .plan import Builder, Plan, Rt
+from .plan import Builder, Plan, Rt, read_options
 
 _CACHE_ATTR = "_yms_plans"
 
@@ -49,14 +48,15 @@ def _check_inputs(inputs):
 
 
 def get_plan(module, inputs, dt, training):
-    key = (tuple(tuple(x.shape) for x in inputs), tuple(bool(x.requires_grad) for x in inputs), dt, training)
+    opts = read_options()
+    key = (tuple(tuple(x.shape) for x in inputs), tuple(bool(x.requires_grad) for x in inputs), dt, training, opts)
     cache = module.__dict__.setdefault(_CACHE_ATTR, {})
     plan = cache.get(key)
     if plan is None:
         for x in inputs:
             if x.dim() != 4:
                 raise RuntimeError(f"yms: expected NCHW 4-D input, got shape {tuple(x.shape)}")
-        b = Builder(inputs[0].shape[0], L.dtype_code(dt), training)
+        b = Builder(inputs[0].shape[0], L.dtype_code(dt), training, opts)
         in_views, outs, kind = module._yms_plan(b, inputs)
         for v, x in zip(in_views, inputs):
             v.buf.name = "input"
@@ -93,7 +93,6 @@ def _decode(plan, rt, arena):
     nc = info["nc"]
     A = sum(v.h * v.w for v in views)
     out = torch.empty((n, A, 4 + nc), dtype=torch.float32, device=arena.device)
-    import ctypes
     lv = (ctypes.c_void_p * 4)(*[rt.a(v) for v in views] + [None] * (4 - len(views)))
     hs = (ctypes.c_int * 4)(*[v.h for v in views] + [0] * (4 - len(views)))
     ws = (ctypes.c_int * 4)(*[v.w for v in views] + [0] * (4 - len(views)))
@@ -116,7 +115,7 @@ def _seed_grad(plan, rt, v, g, acc):
     n, c, h, w = g.shape
     if (g.dtype == L_DTYPES[plan.dt] and g.stride(1) == 1 and g.stride(3) == c and g.stride(2) == w * c
             and g.stride(0) == h * w * c and not acc and c == v.buf.ld and v.off == 0):
-        if os.environ.get("YMS_GRAD_INPLACE", "1") != "0" and v.buf.idx in plan.grad_read_only and not any(v2.buf is v.buf for v2 in plan.outputs if v2 is not v):
+        if plan.opts.grad_inplace and v.buf.idx in plan.grad_read_only and not any(v2.buf is v.buf for v2 in plan.outputs if v2 is not v):
             if rt.gover is None:
                 rt.gover = {}
             rt.gover[v.buf.idx] = g.data_ptr()
@@ -128,8 +127,7 @@ def _seed_grad(plan, rt, v, g, acc):
            v.off, acc, rt.st)
 
 
-# weight-gradient GEMMs on a per-device side stream (YMS_WGRAD_STREAM=0: all on one stream)
-WGRAD_SIDE_STREAM = os.environ.get("YMS_WGRAD_STREAM", "1") != "0"
+# weight-gradient GEMMs on a per-device side stream (plan.opts.wgrad_stream off: all on one stream)
 _SIDE = {}
 
 
@@ -154,7 +152,7 @@ class _PlanFn(torch.autograd.Function):
         rt = Rt(plan, arena.data_ptr(), stream, True)
         _load_inputs(plan, rt, inputs)
         ops = plan.ops
-        if WGRAD_SIDE_STREAM and plan.ops and plan.ops[0] in plan.stem_inputs.values():
+        if plan.opts.wgrad_stream and plan.ops and plan.ops[0] in plan.stem_inputs.values():
             # the stem conv reads the fp32 weight itself: the step's weight packs go to the side
             # stream and overlap it; every later conv is ordered after them
             main, side = torch.cuda.current_stream(dev), _side_stream(dev)
@@ -192,7 +190,7 @@ class _PlanFn(torch.autograd.Function):
         dev = state.arena.device
         rt.st = L.stream_ptr(dev)
         rt.main = torch.cuda.current_stream(dev)
-        rt.side = _side_stream(dev) if WGRAD_SIDE_STREAM else None
+        rt.side = _side_stream(dev) if plan.opts.wgrad_stream else None
         garena = torch.empty(max(plan.garena_bytes, 1), dtype=torch.uint8, device=dev)
         rt.gbase = garena.data_ptr()
         rt.gover = None
@@ -209,15 +207,14 @@ class _PlanFn(torch.autograd.Function):
         # requires_grad pattern, and the per-parameter torch views are built only after the
         # backward's kernels are enqueued (that host loop used to leave the GPU idle ~0.5 ms)
         need = tuple(p.requires_grad for p in params)
-        lays = plan.__dict__.setdefault("_pg_layouts", {})
-        lay = lays.get(need)
+        lay = plan._pg_layouts.get(need)
         if lay is None:
             offs, off = [], 0
             for i in plan.pgrad_order:
                 if need[i]:
                     offs.append((i, off, params[i].numel(), tuple(params[i].shape)))
                     off += params[i].numel()
-            lay = lays[need] = (off, offs)
+            lay = plan._pg_layouts[need] = (off, offs)
         total, offs = lay
         pg = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
         base = pg.data_ptr()
@@ -303,7 +300,7 @@ def run(module, inputs, grad_hook=None):
         # thread pool churning through threads does not keep one full arena per dead thread)
         arena = None
         if decode:
-            cache = plan.__dict__.setdefault("_infer_arenas", {})
+            cache = plan._infer_arenas
             key = (stream, threading.get_ident())
             arena = cache.pop(key, None)
             if arena is not None and arena.device != dev:
@@ -326,12 +323,9 @@ def run(module, inputs, grad_hook=None):
 
 def _bump_bn_counters(plan):
     """nn.BatchNorm2d increments num_batches_tracked in training forward."""
-    ts = getattr(plan, "_nbt", None)
+    ts = plan._nbt
     if ts is None:
-        from .plan import ConvOp, SiblingConvOp
-        ts = [m.bn.num_batches_tracked for op in plan.ops
-              for m in (op.bn_modules() if isinstance(op, SiblingConvOp) else (op.mod,) if isinstance(op, ConvOp) else ())]
-        plan._nbt = ts
+        ts = plan._nbt = [m.bn.num_batches_tracked for op in plan.ops for m in op.bn_modules()]
     if ts:
         with torch.no_grad():
             torch._foreach_add_(ts, 1)
