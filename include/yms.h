@@ -144,6 +144,34 @@ yms_status yms_conv_dgrad_bnred(const yms_conv_shape* s, const void* dz, int dz_
                                 const void* wpacked_t, void* dx, int dx_ld, int dx_off, int accumulate,
                                 const void* z, int z_ld, int z_off, const float* scale, const float* shift,
                                 const float* mean_invstd, int act, float* ws, void* stream);
+/* Grouped launches: njobs INDEPENDENT convolutions (host array of jobs, each the arguments of the
+ * solo call) in as few launches as their kernels allow.  Jobs that share one kernel variant (dtype,
+ * k, epilogue, tile shape, loader) run up to four per launch, every member decomposed exactly as its
+ * solo call (same tiles per block, same statistics rows), so every output and statistics row is
+ * bit-identical to njobs solo calls; the other jobs (fp32, the direct 3x3 route, stride-2 input
+ * gradients, outputs of <= 32 channels, a job alone in its variant) go through the solo call. */
+typedef struct {
+  yms_conv_shape shape;
+  const void* x; int x_ld, x_off;
+  const void* wpacked;
+  void* y; int y_ld, y_off;
+  const float* scale; const float* shift; int act;
+  const void* res; int res_ld, res_off;
+  float* stats;
+} yms_conv_fwd_job;
+typedef struct {
+  yms_conv_shape shape;
+  const void* dz; int dz_ld, dz_off;
+  const void* wpacked_t;
+  void* dx; int dx_ld, dx_off;
+  int accumulate;
+} yms_conv_dgrad_job;
+yms_status yms_conv_fwd_group(int njobs, const yms_conv_fwd_job* jobs, void* stream);
+yms_status yms_conv_dgrad_group(int njobs, const yms_conv_dgrad_job* jobs, void* stream);
+/* Host only: the number of calls the grouped call makes for these jobs (grouped launches + solo
+ * calls; -1: invalid jobs). */
+int yms_conv_fwd_group_launches(int njobs, const yms_conv_fwd_job* jobs);
+int yms_conv_dgrad_group_launches(int njobs, const yms_conv_dgrad_job* jobs);
 /* dw[cout][cin][k][k] (+)= sum_pixels x (*) dz, fp32; ws = split-K partial slabs. */
 size_t yms_conv_wgrad_ws_bytes(const yms_conv_shape* s);
 yms_status yms_conv_wgrad(const yms_conv_shape* s, const void* x, int x_ld, int x_off,
@@ -204,6 +232,44 @@ yms_status yms_bn_act_bwd_reduce_finalize(int dtype, long npix, int c, const voi
  * counter as above). */
 yms_status yms_bias_bwd(int dtype, long npix, int c, const void* gy, int gy_ld, int gy_off,
                         float* ws, unsigned* counter, float* dbias, void* stream);
+/* Grouped forms of the passes above: njobs INDEPENDENT jobs (host array, each the arguments of the solo
+ * call), up to eight per launch.  Every member keeps its solo launch's block count and per-block
+ * pixel ranges / partial rows, so all outputs are bit-identical to njobs solo calls.  A job alone in
+ * the call, a finalize of more than 1024 rows and a reduce without z take the solo call.
+ * yms_bn_pass_job serves the four per-pixel passes:
+ *   affine:  z, scale, shift, act, res (read, optional) -> out = y
+ *   reduce:  z, gy, scale, shift, mean_invstd, act -> ws
+ *   apply:   z, gy, scale, shift, mean_invstd, coef, act -> out = dz; res = gres (res_acc), optional
+ *   bias:    gy -> dbias (ws, counter as yms_bias_bwd) */
+typedef struct {
+  int c;
+  float* stats; int rows, stats_ld; long count;
+  const float* gamma; const float* beta; float* rmean; float* rvar;
+  float momentum, eps;
+  float* mean_invstd; int mi_ld;
+  float* scale; float* shift;
+} yms_bn_finalize_job;
+typedef struct {
+  long npix; int c;
+  const void* z; int z_ld, z_off;
+  const void* gy; int gy_ld, gy_off;
+  const float* scale; const float* shift; const float* mean_invstd; const float* coef;
+  int act;
+  void* out; int out_ld, out_off;
+  void* res; int res_ld, res_off, res_acc;
+  float* ws; unsigned* counter; float* dbias;
+} yms_bn_pass_job;
+typedef struct {
+  int c;
+  const float* ws; int rows; long count;
+  float* dgamma; float* dbeta; float* coef;
+} yms_bn_bwd_finalize_job;
+yms_status yms_bn_finalize_group(int njobs, const yms_bn_finalize_job* jobs, void* stream);
+yms_status yms_affine_act_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream);
+yms_status yms_bn_act_bwd_reduce_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream);
+yms_status yms_bn_act_bwd_finalize_group(int njobs, const yms_bn_bwd_finalize_job* jobs, void* stream);
+yms_status yms_bn_act_bwd_apply_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream);
+yms_status yms_bias_bwd_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream);
 
 /* ---- SPPF pools / upsample / layout ---------------------------------------------------- */
 /* buf holds 4 consecutive channel slots of width c at channel offset off: slot0 = input x,

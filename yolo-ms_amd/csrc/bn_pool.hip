@@ -10,6 +10,7 @@
 //   Upsample nearest x2                                 yolov8/model/components.py:159-160
 #include <cstdlib>
 #include <algorithm>
+#include <vector>
 
 #include "yms_common.hpp"
 
@@ -73,6 +74,26 @@ struct Moments {           // n, sum n_r (m_r - K), sum [M2_r + n_r (m_r - K)^2]
     return m;
   }
 };
+
+// Grouped launches of the passes below: up to BN_GROUP_MAX independent jobs in one launch.  The
+// blocks of member j are [first[j], first[j + 1]) of blockIdx.x, so member j's block
+// blockIdx.x - first[j] of first[j + 1] - first[j] does exactly what that block of its solo launch
+// does (same pixel range, same partial row): only the number of launches changes.
+constexpr int BN_GROUP_MAX = 8;
+template <typename Job>
+struct BnGroup {
+  Job job[BN_GROUP_MAX];
+  unsigned first[BN_GROUP_MAX + 1];
+  int n;
+};
+template <typename Job>
+__device__ __forceinline__ int group_member(const BnGroup<Job>& g, unsigned& bid, unsigned& nblk) {
+  int j = 0;
+  while (j + 1 < g.n && blockIdx.x >= g.first[j + 1]) ++j;
+  bid = blockIdx.x - g.first[j];
+  nblk = g.first[j + 1] - g.first[j];
+  return j;
+}
 
 // Pre-reduction for long statistics tables: block (cb, s) merges rows [s*R, (s+1)*R) of
 // channels [64cb, 64cb+64) and stores the merged (sum, M2) over row s*R -- the first row of its
@@ -177,13 +198,13 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(int c, const float* s
 // step-neutral to slightly faster (YOLOv8-s 18.71 / 18.71 -> 18.67 / 18.74 ms, YOLO-MS-S 37.29 /
 // 37.37 -> 37.24 / 37.26 ms, profiles/r03u_bn_finalize_small_ab.txt).
 constexpr int FIN3_RL = 32;
-__global__ __launch_bounds__(256) void bn_finalize_small_kernel(int c, const float* stats, int rows, int ld,
-                                                                long count, const float* g, const float* b, float* rm,
-                                                                float* rv, float momentum, float eps, float* mi,
-                                                                int mi_ld, float* scale, float* shift) {
+__device__ __forceinline__ void bn_finalize_small_body(int c, const float* stats, int rows, int ld, long count,
+                                                       const float* g, const float* b, float* rm, float* rv,
+                                                       float momentum, float eps, float* mi, int mi_ld,
+                                                       float* scale, float* shift, const unsigned bid) {
   __shared__ double red[FIN3_RL * 9][4];
   const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;
-  const int ch = blockIdx.x * 8 + tx;
+  const int ch = bid * 8 + tx;
   const float* cnt = stats + (long)rows * 2 * ld;
   Moments a;
   if (ch < c) {
@@ -220,6 +241,27 @@ __global__ __launch_bounds__(256) void bn_finalize_small_kernel(int c, const flo
     scale[ch] = sc;
     shift[ch] = b[ch] - (float)mean * sc;
   }
+}
+__global__ __launch_bounds__(256) void bn_finalize_small_kernel(int c, const float* stats, int rows, int ld,
+                                                                long count, const float* g, const float* b, float* rm,
+                                                                float* rv, float momentum, float eps, float* mi,
+                                                                int mi_ld, float* scale, float* shift) {
+  bn_finalize_small_body(c, stats, rows, ld, count, g, b, rm, rv, momentum, eps, mi, mi_ld, scale, shift, blockIdx.x);
+}
+struct FinJob {
+  int c, rows, ld, mi_ld;
+  const float* stats;
+  long count;
+  const float *g, *b;
+  float *rm, *rv;
+  float momentum, eps;
+  float *mi, *scale, *shift;
+};
+__global__ __launch_bounds__(256) void bn_finalize_small_group_kernel(BnGroup<FinJob> grp) {
+  unsigned bid, nblk;
+  const FinJob& j = grp.job[group_member(grp, bid, nblk)];
+  bn_finalize_small_body(j.c, j.stats, j.rows, j.ld, j.count, j.g, j.b, j.rm, j.rv, j.momentum, j.eps, j.mi, j.mi_ld,
+                         j.scale, j.shift, bid);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -265,24 +307,25 @@ constexpr bool BN_REV_AFFINE = true, BN_REV_RED = false, BN_REV_APPLY = false;
 // beside it (the backward apply's gy and z, the forward affine's z; the reduce's reads stay cached:
 // the apply re-reads the same bytes next).  Interleaved A/B (profiles/r06s_bn_nt_ab.txt): YOLOv8-s
 // 17.72 -> 17.64 ms/step, YOLO-MS-S 35.56 -> 35.38 ms (each alone gives part of it).
-template <bool REV> __device__ __forceinline__ long block_range() {
-  return REV ? (long)(gridDim.x - 1 - blockIdx.x) : (long)blockIdx.x;
+// (bid of nblk: the launch's own block index and grid size, or a grouped launch's member-relative ones)
+template <bool REV> __device__ __forceinline__ long block_range(unsigned bid, unsigned nblk) {
+  return REV ? (long)(nblk - 1 - bid) : (long)bid;
 }
 
 // PIPE (the default): software-pipelined (c % 8 == 0) like the backward passes: the next U pixels' loads
 // (clamped to the block's last pixel, masked) are in flight while this U is computed and stored.
-template <typename T, bool PIPE = false>
-__global__ __launch_bounds__(256) void affine_act_kernel(long npix, int c, const T* z, int z_ld, int z_off,
-                                                         const float* scale, const float* shift, int act,
-                                                         const T* res, int res_ld, int res_off, T* y,
-                                                         int y_ld, int y_off, long ppb) {
+template <typename T, bool PIPE>
+__device__ __forceinline__ void affine_act_body(long npix, int c, const T* z, int z_ld, int z_off,
+                                                const float* scale, const float* shift, int act, const T* res,
+                                                int res_ld, int res_off, T* y, int y_ld, int y_off, long ppb,
+                                                const unsigned bid, const unsigned nblk) {
   ChanMap m(c);
   if (!m.active) return;
   const int c0 = m.g * 8, nv = min(8, c - c0);
   float sc[8], sh[8];
   load_params8(scale, c0, c, sc, 1.0f);
   load_params8(shift, c0, c, sh, 0.0f);
-  const long p0 = block_range<BN_REV_AFFINE>() * ppb, p1 = min(npix, p0 + ppb);
+  const long p0 = block_range<BN_REV_AFFINE>(bid, nblk) * ppb, p1 = min(npix, p0 + ppb);
   auto emit = [&](long pix, const Raw8<T>& zz, const Raw8<T>& rres, int valid) {
     float v[8], r[8];
     unpack8(zz, v);
@@ -347,6 +390,33 @@ __global__ __launch_bounds__(256) void affine_act_kernel(long npix, int c, const
     }
   }
 }
+template <typename T, bool PIPE = false>
+__global__ __launch_bounds__(256) void affine_act_kernel(long npix, int c, const T* z, int z_ld, int z_off,
+                                                         const float* scale, const float* shift, int act,
+                                                         const T* res, int res_ld, int res_off, T* y,
+                                                         int y_ld, int y_off, long ppb) {
+  affine_act_body<T, PIPE>(npix, c, z, z_ld, z_off, scale, shift, act, res, res_ld, res_off, y, y_ld, y_off, ppb,
+                           blockIdx.x, gridDim.x);
+}
+// One elementwise / reduce job of a grouped launch (affine: out = y, res read; reduce: ws; apply:
+// out = dz, res = gres; the bias reduce: fin)
+struct PassJob {
+  long npix, ppb;
+  int c, act;
+  const void* z; int z_ld, z_off;
+  const void* gy; int gy_ld, gy_off;
+  const float *scale, *shift, *mi, *coef;
+  void* out; int out_ld, out_off;
+  void* res; int res_ld, res_off, res_acc;
+  float* ws;
+};
+template <typename T, bool PIPE>
+__global__ __launch_bounds__(256) void affine_act_group_kernel(BnGroup<PassJob> grp) {
+  unsigned bid, nblk;
+  const PassJob& j = grp.job[group_member(grp, bid, nblk)];
+  affine_act_body<T, PIPE>(j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, j.scale, j.shift, j.act, (const T*)j.res,
+                           j.res_ld, j.res_off, (T*)j.out, j.out_ld, j.out_off, j.ppb, bid, nblk);
+}
 
 // ------------------------------------------------------------------------------------------
 // BN + SiLU backward.  Each block owns a contiguous pixel range and writes one partial row
@@ -359,12 +429,11 @@ struct BwdFin {          // fused finalize (FIN): the last reduce block to finis
 };
 
 // PIPE = false: the serial loop for every c (c % 8 != 0 tails; the host launches PIPE = true)
-template <typename T, bool HAS_Z, bool FIN = false, bool PIPE = true>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, const T* z, int z_ld,
-                                                            int z_off, const T* gy, int gy_ld, int gy_off,
-                                                            const float* scale, const float* shift,
-                                                            const float* mi, int act, float* ws, long ppb,
-                                                            BwdFin fin = BwdFin{}) {
+template <typename T, bool HAS_Z, bool FIN, bool PIPE>
+__device__ __forceinline__ void bn_bwd_reduce_body(long npix, int c, const T* z, int z_ld, int z_off, const T* gy,
+                                                   int gy_ld, int gy_off, const float* scale, const float* shift,
+                                                   const float* mi, int act, float* ws, long ppb, const BwdFin& fin,
+                                                   const unsigned bid, const unsigned nblk) {
   __shared__ float red[2][2048 + 64];
   ChanMap m(c);
   const int c0 = m.g * 8, nv = min(8, c - c0);
@@ -379,7 +448,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, co
       load_params8(mi, c0, c, mu, 0.f);
       load_params8(mi + c, c0, c, is, 0.f);
     }
-    const long p0 = block_range<BN_REV_RED>() * ppb, p1 = min(npix, p0 + ppb);
+    const long p0 = block_range<BN_REV_RED>(bid, nblk) * ppb, p1 = min(npix, p0 + ppb);
     auto accum = [&](const Raw8<T>& g, const Raw8<T>& zz) {
       float gv[8], zv[8];
       unpack8(g, gv);
@@ -463,11 +532,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, co
       float t1 = 0.f, t2 = 0.f;
       for (int l = 0; l < lanes; ++l) { t1 += red[0][l * W + ch]; t2 += red[1][l * W + ch]; }
       if (lane0 == 0) {
-        ws[block_range<BN_REV_RED>() * 2 * c + ch] = t1;          // row = the block's pixel range
-        ws[block_range<BN_REV_RED>() * 2 * c + c + ch] = t2;
+        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + ch] = t1;          // row = the block's pixel range
+        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + c + ch] = t2;
       } else {
-        ws[block_range<BN_REV_RED>() * 2 * c + ch] += t1;
-        ws[block_range<BN_REV_RED>() * 2 * c + c + ch] += t2;
+        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + ch] += t1;
+        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + c + ch] += t2;
       }
     }
     __syncthreads();
@@ -483,7 +552,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, co
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const unsigned t = __hip_atomic_fetch_add(fin.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned last = (t == gridDim.x - 1) ? 1u : 0u;
+      const unsigned last = (t == nblk - 1) ? 1u : 0u;
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -493,7 +562,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, co
     __syncthreads();
     if (flag[0] == 0) return;
     __syncthreads();
-    const int rows = gridDim.x, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int rows = nblk, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     double* dred = reinterpret_cast<double*>(&red[0][0]);     // [2][8][33] doubles
     for (int cb = 0; cb < c; cb += 32) {
       const int ch = cb + tx;
@@ -530,16 +599,48 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, co
     if (threadIdx.x == 0) __hip_atomic_store(fin.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
+template <typename T, bool HAS_Z, bool FIN = false, bool PIPE = true>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, const T* z, int z_ld,
+                                                            int z_off, const T* gy, int gy_ld, int gy_off,
+                                                            const float* scale, const float* shift,
+                                                            const float* mi, int act, float* ws, long ppb,
+                                                            BwdFin fin = BwdFin{}) {
+  bn_bwd_reduce_body<T, HAS_Z, FIN, PIPE>(npix, c, z, z_ld, z_off, gy, gy_ld, gy_off, scale, shift, mi, act, ws, ppb,
+                                          fin, blockIdx.x, gridDim.x);
+}
+// grouped: the BN + act reduce (HAS_Z, separate finalize) ...
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_group_kernel(BnGroup<PassJob> grp) {
+  unsigned bid, nblk;
+  const PassJob& j = grp.job[group_member(grp, bid, nblk)];
+  bn_bwd_reduce_body<T, true, false, true>(j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, (const T*)j.gy, j.gy_ld,
+                                           j.gy_off, j.scale, j.shift, j.mi, j.act, j.ws, j.ppb, BwdFin{}, bid, nblk);
+}
+// ... and the bias reduce with its in-launch finalize (each member its own arrival counter)
+struct BiasJob {
+  long npix, ppb;
+  int c;
+  const void* gy; int gy_ld, gy_off;
+  float* ws;
+  BwdFin fin;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void bias_bwd_group_kernel(BnGroup<BiasJob> grp) {
+  unsigned bid, nblk;
+  const BiasJob& j = grp.job[group_member(grp, bid, nblk)];
+  bn_bwd_reduce_body<T, false, true, true>(j.npix, j.c, (const T*)nullptr, 0, 0, (const T*)j.gy, j.gy_ld, j.gy_off,
+                                           nullptr, nullptr, nullptr, YMS_ACT_NONE, j.ws, j.ppb, j.fin, bid, nblk);
+}
 
 // 32 channels x TY row lanes per block.  TY = 8 (256 threads) by default: with the weight
 // gradients running on the side stream, a 1024-thread block waits for a whole CU to drain,
 // which puts that wait on the main stream's critical path.
 template <int TY>
-__global__ __launch_bounds__(32 * TY) void bn_bwd_finalize_kernel(int c, const float* ws, int rows, long count,
-                                                                  float* dgamma, float* dbeta, float* coef) {
+__device__ __forceinline__ void bn_bwd_finalize_body(int c, const float* ws, int rows, long count, float* dgamma,
+                                                     float* dbeta, float* coef, const unsigned bid) {
   __shared__ double red[2][TY][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int ch = blockIdx.x * 32 + tx;
+  const int ch = bid * 32 + tx;
   double a1[4] = {0, 0, 0, 0}, a2[4] = {0, 0, 0, 0};
   if (ch < c) {
     int r = ty;
@@ -569,19 +670,34 @@ __global__ __launch_bounds__(32 * TY) void bn_bwd_finalize_kernel(int c, const f
     }
   }
 }
-
+template <int TY>
+__global__ __launch_bounds__(32 * TY) void bn_bwd_finalize_kernel(int c, const float* ws, int rows, long count,
+                                                                  float* dgamma, float* dbeta, float* coef) {
+  bn_bwd_finalize_body<TY>(c, ws, rows, count, dgamma, dbeta, coef, blockIdx.x);
+}
+struct BwdFinJob {
+  int c, rows;
+  const float* ws;
+  long count;
+  float *dgamma, *dbeta, *coef;
+};
+template <int TY>
+__global__ __launch_bounds__(32 * TY) void bn_bwd_finalize_group_kernel(BnGroup<BwdFinJob> grp) {
+  unsigned bid, nblk;
+  const BwdFinJob& j = grp.job[group_member(grp, bid, nblk)];
+  bn_bwd_finalize_body<TY>(j.c, j.ws, j.rows, j.count, j.dgamma, j.dbeta, j.coef, bid);
+}
 
 // PIPE (the default): software-pipelined like the reduce (c % 8 == 0): the next U pixels' loads (clamped to
 // the block's last pixel, masked) are in flight while this U is computed and stored.  Stores stay
 // masked: dz may overwrite z in place and gres may accumulate, so a duplicate pixel must not be
 // written twice.
-template <typename T, bool PIPE = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long npix, int c, const T* z, int z_ld, int z_off,
-                                                           const T* gy, int gy_ld, int gy_off, const float* scale,
-                                                           const float* shift, const float* mi,
-                                                           const float* coef, int act, T* dz, int dz_ld,
-                                                           int dz_off, T* gres, int gres_ld, int gres_off,
-                                                           int gres_acc, long ppb) {
+template <typename T, bool PIPE>
+__device__ __forceinline__ void bn_bwd_apply_body(long npix, int c, const T* z, int z_ld, int z_off, const T* gy,
+                                                  int gy_ld, int gy_off, const float* scale, const float* shift,
+                                                  const float* mi, const float* coef, int act, T* dz, int dz_ld,
+                                                  int dz_off, T* gres, int gres_ld, int gres_off, int gres_acc,
+                                                  long ppb, const unsigned bid, const unsigned nblk) {
   ChanMap m(c);
   if (!m.active) return;
   const int c0 = m.g * 8, nv = min(8, c - c0);
@@ -601,7 +717,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long npix, int c, con
       A[i] = -sc[i] * k0[i] - Bz[i] * mu[i];
     }
   }
-  const long p0 = block_range<BN_REV_APPLY>() * ppb, p1 = min(npix, p0 + ppb);
+  const long p0 = block_range<BN_REV_APPLY>(bid, nblk) * ppb, p1 = min(npix, p0 + ppb);
   const bool racc = gres && gres_acc;
   auto emit = [&](long pix, const Raw8<T>& g, const Raw8<T>& zz, const Raw8<T>& rres, int valid) {
     float gv[8], zv[8], out[8];
@@ -681,6 +797,24 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long npix, int c, con
       }
     }
   }
+}
+template <typename T, bool PIPE = false>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long npix, int c, const T* z, int z_ld, int z_off,
+                                                           const T* gy, int gy_ld, int gy_off, const float* scale,
+                                                           const float* shift, const float* mi,
+                                                           const float* coef, int act, T* dz, int dz_ld,
+                                                           int dz_off, T* gres, int gres_ld, int gres_off,
+                                                           int gres_acc, long ppb) {
+  bn_bwd_apply_body<T, PIPE>(npix, c, z, z_ld, z_off, gy, gy_ld, gy_off, scale, shift, mi, coef, act, dz, dz_ld, dz_off,
+                             gres, gres_ld, gres_off, gres_acc, ppb, blockIdx.x, gridDim.x);
+}
+template <typename T, bool PIPE>
+__global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(BnGroup<PassJob> grp) {
+  unsigned bid, nblk;
+  const PassJob& j = grp.job[group_member(grp, bid, nblk)];
+  bn_bwd_apply_body<T, PIPE>(j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, (const T*)j.gy, j.gy_ld, j.gy_off, j.scale,
+                             j.shift, j.mi, j.coef, j.act, (T*)j.out, j.out_ld, j.out_off, (T*)j.res, j.res_ld,
+                             j.res_off, j.res_acc, j.ppb, bid, nblk);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1128,6 +1262,217 @@ yms_status yms_bias_bwd(int dtype, long npix, int c, const void* gy, int gy_ld, 
                         float* ws, unsigned* counter, float* dbias, void* stream) {
   return yms_bn_act_bwd_reduce_finalize(dtype, npix, c, nullptr, 0, 0, gy, gy_ld, gy_off, nullptr, nullptr,
                                         nullptr, YMS_ACT_NONE, ws, counter, nullptr, dbias, nullptr, stream);
+}
+
+}  // extern "C"
+
+// ---- grouped forms: the jobs the grouped kernel serves go out BN_GROUP_MAX per launch, each member
+// with its solo launch's block count and per-block ranges; a job alone, or one the grouped kernel does
+// not serve, takes the solo call (solo(i)), in job order after the grouped launches
+template <typename Job, typename Launch, typename Solo>
+static yms_status launch_bn_groups(int njobs, const std::vector<int>& idx, const std::vector<Job>& jobs,
+                                   const std::vector<unsigned>& blocks, Launch launch, Solo solo) {
+  std::vector<char> grouped(njobs, 0);
+  if (idx.size() >= 2) {
+    for (size_t i = 0; i < idx.size(); i += BN_GROUP_MAX) {
+      const int n = (int)std::min<size_t>(BN_GROUP_MAX, idx.size() - i);
+      if (n < 2) break;                      // a lone remainder: solo
+      BnGroup<Job> g{};
+      g.n = n;
+      for (int k = 0; k < n; ++k) {
+        g.job[k] = jobs[i + k];
+        g.first[k + 1] = g.first[k] + blocks[i + k];
+        grouped[idx[i + k]] = 1;
+      }
+      if (yms_status e = launch(g, g.first[n])) return e;
+      if (yms_status e = launch_status()) return e;
+    }
+  }
+  for (int i = 0; i < njobs; ++i)
+    if (!grouped[i])
+      if (yms_status e = solo(i)) return e;
+  return YMS_OK;
+}
+
+extern "C" {
+
+yms_status yms_bn_finalize_group(int njobs, const yms_bn_finalize_job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<FinJob> js;
+  std::vector<unsigned> blocks;
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_bn_finalize_job& j = jobs[i];
+    if (j.c <= 0 || !j.stats || j.rows <= 0 || j.count <= 0 || !j.gamma || !j.beta || !j.mean_invstd || !j.scale ||
+        !j.shift || j.stats_ld < j.c || j.mi_ld < j.c)
+      return YMS_ERR_INVALID;
+    if (j.rows > 1024) continue;             // long tables: the solo call's pre-reduction + wide finalize
+    js.push_back(FinJob{j.c, j.rows, j.stats_ld, j.mi_ld, j.stats, j.count, j.gamma, j.beta, j.rmean, j.rvar,
+                        j.momentum, j.eps, j.mean_invstd, j.scale, j.shift});
+    blocks.push_back((unsigned)cdiv(j.c, 8));
+    idx.push_back(i);
+  }
+  return launch_bn_groups(
+      njobs, idx, js, blocks,
+      [&](const BnGroup<FinJob>& g, unsigned nb) -> yms_status {
+        hipLaunchKernelGGL(bn_finalize_small_group_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g);
+        return YMS_OK;
+      },
+      [&](int i) {
+        const yms_bn_finalize_job& j = jobs[i];
+        return yms_bn_finalize_ld(j.c, j.stats, j.rows, j.stats_ld, j.count, j.gamma, j.beta, j.rmean, j.rvar,
+                                  j.momentum, j.eps, j.mean_invstd, j.mi_ld, j.scale, j.shift, stream);
+      });
+}
+
+static PassJob pass_job(const yms_bn_pass_job& j, long ppb) {
+  return PassJob{j.npix, ppb, j.c, j.act, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale, j.shift,
+                 j.mean_invstd, j.coef, j.out, j.out_ld, j.out_off, j.res, j.res_ld, j.res_off, j.res_acc, j.ws};
+}
+
+yms_status yms_affine_act_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<PassJob> js;
+  std::vector<unsigned> blocks;
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_bn_pass_job& j = jobs[i];
+    if (j.npix <= 0 || !j.z || !j.out || !vok(j.z_ld, j.z_off, j.c) || !vok(j.out_ld, j.out_off, j.c))
+      return YMS_ERR_INVALID;
+    if (j.res && !vok(j.res_ld, j.res_off, j.c)) return YMS_ERR_INVALID;
+    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
+    const long ppb = elem_ppb(j.npix, j.c, 2);            // as yms_affine_act
+    js.push_back(pass_job(j, ppb));
+    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
+    idx.push_back(i);
+  }
+  return launch_bn_groups(
+      njobs, idx, js, blocks,
+      [&](const BnGroup<PassJob>& g, unsigned nb) -> yms_status {
+        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((affine_act_group_kernel<T, true>), dim3(nb), dim3(256), 0,
+                                                     (hipStream_t)stream, g));
+        return YMS_OK;
+      },
+      [&](int i) {
+        const yms_bn_pass_job& j = jobs[i];
+        return yms_affine_act(dtype, j.npix, j.c, j.z, j.z_ld, j.z_off, j.scale, j.shift, j.act, j.res, j.res_ld,
+                              j.res_off, j.out, j.out_ld, j.out_off, stream);
+      });
+}
+
+yms_status yms_bn_act_bwd_reduce_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<PassJob> js;
+  std::vector<unsigned> blocks;
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_bn_pass_job& j = jobs[i];
+    if (j.npix <= 0 || !j.gy || !j.ws || !vok(j.gy_ld, j.gy_off, j.c)) return YMS_ERR_INVALID;
+    if (j.z && (!vok(j.z_ld, j.z_off, j.c) || !j.scale || !j.shift || !j.mean_invstd)) return YMS_ERR_INVALID;
+    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
+    if (!j.z) continue;                                    // the plain column sum: solo
+    const long ppb = bwd_pix_per_block(j.npix, j.c, false);
+    js.push_back(pass_job(j, ppb));
+    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
+    idx.push_back(i);
+  }
+  return launch_bn_groups(
+      njobs, idx, js, blocks,
+      [&](const BnGroup<PassJob>& g, unsigned nb) -> yms_status {
+        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(bn_bwd_reduce_group_kernel<T>, dim3(nb), dim3(256), 0,
+                                                     (hipStream_t)stream, g));
+        return YMS_OK;
+      },
+      [&](int i) {
+        const yms_bn_pass_job& j = jobs[i];
+        return yms_bn_act_bwd_reduce(dtype, j.npix, j.c, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale,
+                                     j.shift, j.mean_invstd, j.act, j.ws, stream);
+      });
+}
+
+yms_status yms_bn_act_bwd_finalize_group(int njobs, const yms_bn_bwd_finalize_job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<BwdFinJob> js;
+  std::vector<unsigned> blocks;
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_bn_bwd_finalize_job& j = jobs[i];
+    if (j.c <= 0 || !j.ws || j.rows <= 0 || j.count <= 0) return YMS_ERR_INVALID;
+    js.push_back(BwdFinJob{j.c, j.rows, j.ws, j.count, j.dgamma, j.dbeta, j.coef});
+    blocks.push_back((unsigned)cdiv(j.c, 32));
+    idx.push_back(i);
+  }
+  return launch_bn_groups(
+      njobs, idx, js, blocks,
+      [&](const BnGroup<BwdFinJob>& g, unsigned nb) -> yms_status {
+        hipLaunchKernelGGL(bn_bwd_finalize_group_kernel<8>, dim3(nb), dim3(256), 0, (hipStream_t)stream, g);
+        return YMS_OK;
+      },
+      [&](int i) {
+        const yms_bn_bwd_finalize_job& j = jobs[i];
+        return yms_bn_act_bwd_finalize(j.c, j.ws, j.rows, j.count, j.dgamma, j.dbeta, j.coef, stream);
+      });
+}
+
+yms_status yms_bn_act_bwd_apply_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<PassJob> js;
+  std::vector<unsigned> blocks;
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_bn_pass_job& j = jobs[i];
+    if (j.npix <= 0 || !j.z || !j.gy || !j.out || !j.scale || !j.shift || !j.mean_invstd || !j.coef)
+      return YMS_ERR_INVALID;
+    if (!vok(j.z_ld, j.z_off, j.c) || !vok(j.gy_ld, j.gy_off, j.c) || !vok(j.out_ld, j.out_off, j.c))
+      return YMS_ERR_INVALID;
+    if (j.res && !vok(j.res_ld, j.res_off, j.c)) return YMS_ERR_INVALID;
+    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
+    const long ppb = elem_ppb(j.npix, j.c, 8 * BN_U / BN_UA);   // as yms_bn_act_bwd_apply
+    js.push_back(pass_job(j, ppb));
+    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
+    idx.push_back(i);
+  }
+  return launch_bn_groups(
+      njobs, idx, js, blocks,
+      [&](const BnGroup<PassJob>& g, unsigned nb) -> yms_status {
+        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_apply_group_kernel<T, true>), dim3(nb), dim3(256), 0,
+                                                     (hipStream_t)stream, g));
+        return YMS_OK;
+      },
+      [&](int i) {
+        const yms_bn_pass_job& j = jobs[i];
+        return yms_bn_act_bwd_apply(dtype, j.npix, j.c, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale,
+                                    j.shift, j.mean_invstd, j.coef, j.act, j.out, j.out_ld, j.out_off, j.res,
+                                    j.res_ld, j.res_off, j.res_acc, stream);
+      });
+}
+
+yms_status yms_bias_bwd_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<BiasJob> js;
+  std::vector<unsigned> blocks;
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_bn_pass_job& j = jobs[i];
+    if (j.npix <= 0 || !j.gy || !j.ws || !j.counter || !vok(j.gy_ld, j.gy_off, j.c)) return YMS_ERR_INVALID;
+    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
+    const long ppb = bwd_pix_per_block(j.npix, j.c, true);       // as yms_bn_act_bwd_reduce_finalize
+    js.push_back(BiasJob{j.npix, ppb, j.c, j.gy, j.gy_ld, j.gy_off, j.ws,
+                         BwdFin{j.counter, nullptr, j.dbias, nullptr, j.npix}});
+    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
+    idx.push_back(i);
+  }
+  return launch_bn_groups(
+      njobs, idx, js, blocks,
+      [&](const BnGroup<BiasJob>& g, unsigned nb) -> yms_status {
+        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(bias_bwd_group_kernel<T>, dim3(nb), dim3(256), 0,
+                                                     (hipStream_t)stream, g));
+        return YMS_OK;
+      },
+      [&](int i) {
+        const yms_bn_pass_job& j = jobs[i];
+        return yms_bias_bwd(dtype, j.npix, j.c, j.gy, j.gy_ld, j.gy_off, j.ws, j.counter, j.dbias, stream);
+      });
 }
 
 size_t yms_sppf_ws_bytes(int n, int h, int w, int c) {

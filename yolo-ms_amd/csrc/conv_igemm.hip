@@ -16,6 +16,9 @@
 // [32 pixels][cols] and read with ds_read_b64_tr_b16 (hardware transpose) so both
 // operands get 8 consecutive pixels per lane.  wgrad is split over pixels into fp32
 // partial slabs that a second kernel reduces deterministically (no atomics).
+#include <algorithm>
+#include <vector>
+
 #include "conv_common.hpp"
 #include "conv_direct.hpp"
 #include "wgrad_halo.hpp"
@@ -415,8 +418,10 @@ __global__ __launch_bounds__(256, 2) void conv_nt_kernel(NTParams p) {
 // 16-B row segments (+ residual / + accumulate in fp32).
 // ------------------------------------------------------------------------------------------
 constexpr int NTP_MAX_AFFINE_COLS = 512;   // wider affine outputs use conv_nt_kernel
-template <typename T, int KS, int MODE, int EPI, int BM, int BN, int WGM, int WGN, int ST, bool UNI, int OCC = 2>
-__global__ __launch_bounds__(WGM * WGN * 64, OCC) void conv_ntp_kernel(NTParams p) {
+// The kernel body as a function of (parameters, block index, grid size G): conv_ntp_kernel runs it
+// with its own launch's (blockIdx.x, gridDim.x), conv_ntp_group_kernel with one member's.
+template <typename T, int KS, int MODE, int EPI, int BM, int BN, int WGM, int WGN, int ST, bool UNI>
+__device__ __forceinline__ void conv_ntp_body(const NTParams& p, const int bid, const int G) {
   constexpr int NTHR = WGM * WGN * 64;
   constexpr int RPP = NTHR / NT_KCH;                       // rows per load pass (one slot)
   constexpr int SLOT = RPP * 128;                          // LDS bytes per slot
@@ -461,8 +466,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void conv_ntp_kernel(NTParams 
     dv_w = p.cls_div_w[cls];
     dv_hw = p.cls_div_hw[cls];
   }
-  const int G = gridDim.x;
-  const int lb = xcd_remap(blockIdx.x, G);
+  const int lb = xcd_remap(bid, G);
   const int ntiles = ((M + BM - 1) / BM) * p.tiles_n;
   if (lb >= ntiles || nkt <= 0) return;
   const int my_tiles = (ntiles - lb + G - 1) / G;
@@ -794,6 +798,30 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void conv_ntp_kernel(NTParams 
       if (n0 == 0 && c == 0) p.stats_cnt[row] = run[tid];
     }
   }
+}
+
+template <typename T, int KS, int MODE, int EPI, int BM, int BN, int WGM, int WGN, int ST, bool UNI, int OCC = 2>
+__global__ __launch_bounds__(WGM * WGN * 64, OCC) void conv_ntp_kernel(NTParams p) {
+  conv_ntp_body<T, KS, MODE, EPI, BM, BN, WGM, WGN, ST, UNI>(p, blockIdx.x, gridDim.x);
+}
+
+// Up to NT_GROUP_MAX independent convolutions of one template key in ONE launch: member
+// blockIdx.z runs exactly its solo launch's decomposition (its own grid size grid[z] as G, so the
+// same tile -> block walk and the same statistics slots); gridDim.x is the largest member grid and
+// the blocks past a member's own grid leave at once.  (NTGroup is 4 x sizeof(NTParams) + 16 bytes
+// of kernel arguments, within the 4 KB limit: static_assert below.)
+constexpr int NT_GROUP_MAX = 4;
+struct NTGroup {
+  NTParams m[NT_GROUP_MAX];
+  int grid[NT_GROUP_MAX];
+};
+static_assert(sizeof(NTGroup) <= 4096, "NTGroup must fit the kernel-argument segment");
+template <typename T, int KS, int MODE, int EPI, int BM, int BN, int WGM, int WGN, int ST, bool UNI, int OCC = 2>
+__global__ __launch_bounds__(WGM * WGN * 64, OCC) void conv_ntp_group_kernel(NTGroup g) {
+  const int z = blockIdx.z;
+  const int G = g.grid[z];
+  if ((int)blockIdx.x >= G) return;
+  conv_ntp_body<T, KS, MODE, EPI, BM, BN, WGM, WGN, ST, UNI>(g.m[z], blockIdx.x, G);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1518,23 +1546,16 @@ int yms_conv_stats_ld(const yms_conv_shape* s) {
   return (int)rup(s->cout, 128);
 }
 
-yms_status yms_conv_fwd(const yms_conv_shape* s, const void* x, int x_ld, int x_off,
-                        const void* wpacked, void* y, int y_ld, int y_off,
-                        const float* scale, const float* shift, int act,
-                        const void* res, int res_ld, int res_off, float* stats, void* stream) {
-  if (!shape_ok(s) || !x || !wpacked || !y) return YMS_ERR_INVALID;
-  if (!view_ok(x_ld, x_off, s->cin) || !view_ok(y_ld, y_off, s->cout)) return YMS_ERR_INVALID;
-  if (res && !view_ok(res_ld, res_off, s->cout)) return YMS_ERR_INVALID;
+}  // extern "C"
+
+// The implicit-GEMM forward's kernel parameters (everything but tiles_n, which the launch sets from
+// its tile shape): shared by yms_conv_fwd and yms_conv_fwd_group.
+static yms_status fwd_params(const yms_conv_shape* s, const void* x, int x_ld, int x_off, const void* wpacked,
+                             void* y, int y_ld, int y_off, const float* scale, const float* shift, int act,
+                             const void* res, int res_ld, int res_off, float* stats, NTParams& p) {
   const int es = elem_size(s->dtype);
-  {
-    // small-channel 3x3: the direct kernel (conv_direct.hip), statistics included
-    DirectGeo dg;
-    if (conv_direct_geometry(s, 0, &dg))
-      return conv_direct_launch(s, 0, dg, x, x_ld, x_off, wpacked, y, y_ld, y_off, scale, shift, act, res, res_ld,
-                                res_off, stats, 0, (hipStream_t)stream);
-  }
   PackGeo g = pack_geo(s, 0);
-  NTParams p{};
+  p = NTParams{};
   p.src = (const char*)x;
   p.wp = (const char*)wpacked;
   p.dst = (char*)y;
@@ -1553,34 +1574,173 @@ yms_status yms_conv_fwd(const yms_conv_shape* s, const void* x, int x_ld, int x_
   p.Ncols = s->cout;
   p.div_ow = make_fastdiv(s->wo);
   p.div_ohw = make_fastdiv(s->ho * s->wo);
-  (void)es;
+  return YMS_OK;
+}
+
+static bool fwd_args_ok(const yms_conv_shape* s, const void* x, int x_ld, int x_off, const void* wpacked,
+                        const void* y, int y_ld, int y_off, const void* res, int res_ld, int res_off) {
+  if (!shape_ok(s) || !x || !wpacked || !y) return false;
+  if (!view_ok(x_ld, x_off, s->cin) || !view_ok(y_ld, y_off, s->cout)) return false;
+  return !res || view_ok(res_ld, res_off, s->cout);
+}
+
+extern "C" {
+
+yms_status yms_conv_fwd(const yms_conv_shape* s, const void* x, int x_ld, int x_off,
+                        const void* wpacked, void* y, int y_ld, int y_off,
+                        const float* scale, const float* shift, int act,
+                        const void* res, int res_ld, int res_off, float* stats, void* stream) {
+  if (!fwd_args_ok(s, x, x_ld, x_off, wpacked, y, y_ld, y_off, res, res_ld, res_off)) return YMS_ERR_INVALID;
+  {
+    // small-channel 3x3: the direct kernel (conv_direct.hip), statistics included
+    DirectGeo dg;
+    if (conv_direct_geometry(s, 0, &dg))
+      return conv_direct_launch(s, 0, dg, x, x_ld, x_off, wpacked, y, y_ld, y_off, scale, shift, act, res, res_ld,
+                                res_off, stats, 0, (hipStream_t)stream);
+  }
+  NTParams p;
+  if (yms_status e = fwd_params(s, x, x_ld, x_off, wpacked, y, y_ld, y_off, scale, shift, act, res, res_ld, res_off,
+                                stats, p))
+    return e;
   TileChoice tc = choose_tile(s->cout);
   hipStream_t st = (hipStream_t)stream;
   if (stats) return dispatch_nt<MODE_FWD, EPI_STATS>(p, s->dtype, s->k, tc.cfg, st);
   return dispatch_nt<MODE_FWD, EPI_AFFINE>(p, s->dtype, s->k, tc.cfg, st);
 }
 
+}  // extern "C"
+
+static bool dgrad_args_ok(const yms_conv_shape* s, const void* dz, int dz_ld, int dz_off, const void* wpacked_t,
+                          const void* dx, int dx_ld, int dx_off) {
+  if (!shape_ok(s) || !dz || !wpacked_t || !dx) return false;
+  return view_ok(dz_ld, dz_off, s->cout) && view_ok(dx_ld, dx_off, s->cin);
+}
+
+// the input gradient's kernel parameters common to both strides ...
+static void dgrad_params(const yms_conv_shape* s, const void* dz, int dz_ld, int dz_off, const void* wpacked_t,
+                         void* dx, int dx_ld, int dx_off, NTParams& p) {
+  p = NTParams{};
+  p.src = (const char*)dz;
+  p.wp = (const char*)wpacked_t;
+  p.dst = (char*)dx;
+  p.src_ld = dz_ld; p.src_off = dz_off; p.dst_ld = dx_ld; p.dst_off = dx_off;
+  p.SH = s->ho; p.SW = s->wo; p.OW = s->w;
+  p.stride = s->stride; p.pad = s->pad;
+  p.Ncols = s->cin;
+  p.OH = s->h; p.OWx = s->w;
+}
+
+// ... and the stride-1 GEMM's geometry (false: unsupported extent)
+static bool dgrad1_geometry(const yms_conv_shape* s, int dz_ld, NTParams& p) {
+  PackGeo g = pack_geo(s, 1);
+  p.cpt = g.cpt; p.Kc = g.kc; p.nkt = g.nkt;
+  if (!set_src_geometry(p, s->n, s->ho, s->wo, dz_ld, elem_size(s->dtype), g.nkt * NT_KCH)) return false;
+  p.M = s->n * s->h * s->w;
+  p.div_ow = make_fastdiv(s->w);
+  p.div_ohw = make_fastdiv(s->h * s->w);
+  return true;
+}
+
+// One job of a grouped call: key < 0 runs through the solo entry point.
+struct GroupMember {
+  int job, key = -1;
+  NTParams p;
+};
+static bool group_cfg_ok(int cfg) { return cfg == 0 || cfg == 1; }
+static int group_key(int dtype, int ks, int epi, int cfg, bool uni) {
+  return (((dtype * 4 + ks) * 8 + epi) * 4 + cfg) * 2 + (uni ? 1 : 0);
+}
+
+// Mirrors launch_ntp for n members of one key: each member's tiles_n and grid as its solo launch.
+template <typename T, int KS, int MODE, int EPI, bool UNI>
+static void launch_ntp_group(const GroupMember* const* ms, int n, int cfg, hipStream_t st) {
+  const bool stats = EPI == EPI_STATS;
+  const long mult = MODE == MODE_FWD ? nt_fwd_mult(stats) : NT_DGRAD_MULT;
+  const NtpGeo g = ntp_geo(cfg);
+  NTGroup grp{};
+  unsigned gx = 1;
+  for (int i = 0; i < n; ++i) {
+    grp.m[i] = ms[i]->p;
+    grp.m[i].tiles_n = cdiv(grp.m[i].Ncols, g.bn);
+    grp.grid[i] = (int)ntp_grid(grp.m[i].M, grp.m[i].tiles_n, g.bm, g.occ * mult, stats);
+    gx = std::max(gx, (unsigned)grp.grid[i]);
+  }
+  // (forward grids are persistent, so the members' grids are close; input-gradient grids are one
+  // block per tile, so a small member's z-slice is mostly blocks that leave at once -- at B = 64 about
+  // 2400 of 3200 for the 40^2 level and 3000 for the 20^2 one: a dispatch cost of a few microseconds)
+  const dim3 grid(gx, 1, (unsigned)n);
+  if (cfg == 0)
+    hipLaunchKernelGGL((conv_ntp_group_kernel<T, KS, MODE, EPI, 128, 128, 2, 4, 2, UNI, 2>), grid, dim3(512), 0, st, grp);
+  else
+    hipLaunchKernelGGL((conv_ntp_group_kernel<T, KS, MODE, EPI, 128, 64, 4, 2, 2, UNI, 3>), grid, dim3(512), 0, st, grp);
+}
+
+template <int MODE, int EPI>
+static void dispatch_group_epi(const GroupMember* const* ms, int n, hipStream_t st) {
+  const int key = ms[0]->key;
+  const bool uni = key & 1;
+  const int cfg = (key >> 1) & 3, ks = (key >> 6) & 3, dtype = key >> 8;
+#define YMS_GRP_CASE(T)                                                                  \
+  if (ks == 1) {                                                                         \
+    if (uni) launch_ntp_group<T, 1, MODE, EPI, true>(ms, n, cfg, st);                    \
+    else launch_ntp_group<T, 1, MODE, EPI, false>(ms, n, cfg, st);                       \
+  } else {                                                                               \
+    if (uni) launch_ntp_group<T, 3, MODE, EPI, true>(ms, n, cfg, st);                    \
+    else launch_ntp_group<T, 3, MODE, EPI, false>(ms, n, cfg, st);                       \
+  }
+  if (dtype == YMS_BF16) { YMS_GRP_CASE(bf16) }
+  else { YMS_GRP_CASE(f16) }
+#undef YMS_GRP_CASE
+}
+
+// Launches the members key by key (first appearance order), then the solo jobs in job order.
+// count != nullptr: launches nothing and counts the calls it would make (grouped launches + solo calls).
+template <int MODE, typename Solo>
+static yms_status launch_groups(const std::vector<GroupMember>& ms, hipStream_t st, Solo solo, int* count = nullptr) {
+  std::vector<char> done(ms.size(), 0);
+  std::vector<int> singles;
+  for (size_t i = 0; i < ms.size(); ++i) {
+    if (done[i]) continue;
+    if (ms[i].key < 0) { singles.push_back(ms[i].job); continue; }
+    const GroupMember* same[NT_GROUP_MAX];
+    int n = 0;
+    size_t j = i;
+    for (; j < ms.size() && n < NT_GROUP_MAX; ++j)
+      if (!done[j] && ms[j].key == ms[i].key) { same[n++] = &ms[j]; done[j] = 1; }
+    if (n == 1) { singles.push_back(ms[i].job); continue; }
+    if (count) { ++*count; continue; }
+    const int epi = (ms[i].key >> 3) & 7;
+    if (MODE == MODE_FWD) {
+      if (epi == EPI_STATS) dispatch_group_epi<MODE_FWD, EPI_STATS>(same, n, st);
+      else dispatch_group_epi<MODE_FWD, EPI_AFFINE>(same, n, st);
+    } else {
+      if (epi == EPI_ACCUM) dispatch_group_epi<MODE_DGRAD, EPI_ACCUM>(same, n, st);
+      else dispatch_group_epi<MODE_DGRAD, EPI_STORE>(same, n, st);
+    }
+    if (yms_status e = launch_status()) return e;
+  }
+  std::sort(singles.begin(), singles.end());
+  if (count) { *count += (int)singles.size(); return YMS_OK; }
+  for (int i : singles)
+    if (yms_status e = solo(i)) return e;
+  return YMS_OK;
+}
+
+extern "C" {
+
 yms_status yms_conv_dgrad(const yms_conv_shape* s, const void* dz, int dz_ld, int dz_off,
                           const void* wpacked_t, void* dx, int dx_ld, int dx_off,
                           int accumulate, void* stream) {
-  if (!shape_ok(s) || !dz || !wpacked_t || !dx) return YMS_ERR_INVALID;
-  if (!view_ok(dz_ld, dz_off, s->cout) || !view_ok(dx_ld, dx_off, s->cin)) return YMS_ERR_INVALID;
+  if (!dgrad_args_ok(s, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off)) return YMS_ERR_INVALID;
   {
     DirectGeo dg;
     if (conv_direct_geometry(s, 1, &dg))
       return conv_direct_launch(s, 1, dg, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off, nullptr, nullptr, 0,
                                 nullptr, 0, 0, nullptr, accumulate, (hipStream_t)stream);
   }
-  NTParams p{};
-  p.src = (const char*)dz;
-  p.wp = (const char*)wpacked_t;
-  p.dst = (char*)dx;
-  p.src_ld = dz_ld; p.src_off = dz_off; p.dst_ld = dx_ld; p.dst_off = dx_off;
-  p.SH = s->ho; p.SW = s->wo; p.OW = s->w;
+  NTParams p;
+  dgrad_params(s, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off, p);
   if (!offsets32(s->n, s->ho, s->wo, dz_ld)) return YMS_ERR_UNSUPPORTED;
-  p.stride = s->stride; p.pad = s->pad;
-  p.Ncols = s->cin;
-  p.OH = s->h; p.OWx = s->w;
   TileChoice tc = choose_tile(s->cin);
   hipStream_t st = (hipStream_t)stream;
   if (s->stride == 2) {
@@ -1606,15 +1766,83 @@ yms_status yms_conv_dgrad(const yms_conv_shape* s, const void* dz, int dz_ld, in
     if (accumulate) return dispatch_nt<MODE_DGRAD2, EPI_ACCUM>(p, s->dtype, s->k, tc.cfg, st);
     return dispatch_nt<MODE_DGRAD2, EPI_STORE>(p, s->dtype, s->k, tc.cfg, st);
   }
-  PackGeo g = pack_geo(s, 1);
-  p.cpt = g.cpt; p.Kc = g.kc; p.nkt = g.nkt;
-  if (!set_src_geometry(p, s->n, s->ho, s->wo, dz_ld, elem_size(s->dtype), g.nkt * NT_KCH))
-    return YMS_ERR_UNSUPPORTED;
-  p.M = s->n * s->h * s->w;
-  p.div_ow = make_fastdiv(s->w);
-  p.div_ohw = make_fastdiv(s->h * s->w);
+  if (!dgrad1_geometry(s, dz_ld, p)) return YMS_ERR_UNSUPPORTED;
   if (accumulate) return dispatch_nt<MODE_DGRAD, EPI_ACCUM>(p, s->dtype, s->k, tc.cfg, st);
   return dispatch_nt<MODE_DGRAD, EPI_STORE>(p, s->dtype, s->k, tc.cfg, st);
+}
+
+// ---- grouped launches -----------------------------------------------------------------------
+// The jobs of one call are partitioned by kernel template key (dtype, k, epilogue, tile config,
+// UNI loader); each key's members go out NT_GROUP_MAX at a time as one conv_ntp_group_kernel launch.
+// A job alone in its key, and every job the persistent 16-bit kernel does not serve (the direct 3x3
+// route, fp32, the stride-2 input gradient, affine outputs wider than NTP_MAX_AFFINE_COLS, the
+// 32-column tile config, which no grouped caller has needed), runs through its solo entry point, in
+// job order.
+static yms_status fwd_group(int njobs, const yms_conv_fwd_job* jobs, void* stream, int* count) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<GroupMember> ms;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_conv_fwd_job& j = jobs[i];
+    const yms_conv_shape* s = &j.shape;
+    if (!fwd_args_ok(s, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.res, j.res_ld, j.res_off))
+      return YMS_ERR_INVALID;
+    GroupMember m{};
+    m.job = i;
+    DirectGeo dg;
+    const int cfg = choose_tile(s->cout).cfg;
+    const int epi = j.stats ? EPI_STATS : EPI_AFFINE;
+    if (s->dtype != YMS_F32 && !conv_direct_geometry(s, 0, &dg) && group_cfg_ok(cfg) &&
+        (epi != EPI_AFFINE || s->cout <= NTP_MAX_AFFINE_COLS)) {
+      if (yms_status e = fwd_params(s, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.scale, j.shift, j.act,
+                                    j.res, j.res_ld, j.res_off, j.stats, m.p))
+        return e;
+      m.key = group_key(s->dtype, s->k, epi, cfg, m.p.cpt % NT_KCH == 0);
+    }
+    ms.push_back(m);
+  }
+  return launch_groups<MODE_FWD>(ms, (hipStream_t)stream, [&](int i) {
+    const yms_conv_fwd_job& j = jobs[i];
+    return yms_conv_fwd(&j.shape, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.scale, j.shift, j.act, j.res,
+                        j.res_ld, j.res_off, j.stats, stream);
+  }, count);
+}
+yms_status yms_conv_fwd_group(int njobs, const yms_conv_fwd_job* jobs, void* stream) {
+  return fwd_group(njobs, jobs, stream, nullptr);
+}
+int yms_conv_fwd_group_launches(int njobs, const yms_conv_fwd_job* jobs) {
+  int n = 0;
+  return fwd_group(njobs, jobs, nullptr, &n) == YMS_OK ? n : -1;
+}
+
+static yms_status dgrad_group(int njobs, const yms_conv_dgrad_job* jobs, void* stream, int* count) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<GroupMember> ms;
+  for (int i = 0; i < njobs; ++i) {
+    const yms_conv_dgrad_job& j = jobs[i];
+    const yms_conv_shape* s = &j.shape;
+    if (!dgrad_args_ok(s, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off)) return YMS_ERR_INVALID;
+    GroupMember m{};
+    m.job = i;
+    DirectGeo dg;
+    const int cfg = choose_tile(s->cin).cfg;
+    if (s->dtype != YMS_F32 && s->stride == 1 && !conv_direct_geometry(s, 1, &dg) && group_cfg_ok(cfg)) {
+      dgrad_params(s, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off, m.p);
+      if (!offsets32(s->n, s->ho, s->wo, j.dz_ld) || !dgrad1_geometry(s, j.dz_ld, m.p)) return YMS_ERR_UNSUPPORTED;
+      m.key = group_key(s->dtype, s->k, j.accumulate ? EPI_ACCUM : EPI_STORE, cfg, m.p.cpt % NT_KCH == 0);
+    }
+    ms.push_back(m);
+  }
+  return launch_groups<MODE_DGRAD>(ms, (hipStream_t)stream, [&](int i) {
+    const yms_conv_dgrad_job& j = jobs[i];
+    return yms_conv_dgrad(&j.shape, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off, j.accumulate, stream);
+  }, count);
+}
+yms_status yms_conv_dgrad_group(int njobs, const yms_conv_dgrad_job* jobs, void* stream) {
+  return dgrad_group(njobs, jobs, stream, nullptr);
+}
+int yms_conv_dgrad_group_launches(int njobs, const yms_conv_dgrad_job* jobs) {
+  int n = 0;
+  return dgrad_group(njobs, jobs, nullptr, &n) == YMS_OK ? n : -1;
 }
 
 int yms_conv_dgrad_bnred_rows(const yms_conv_shape* s) {

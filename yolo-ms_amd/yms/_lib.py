@@ -45,6 +45,38 @@ class PackJob(ctypes.Structure):
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
+
+
+def _fields(spec):
+    """'name:type ...' -> ctypes _fields_ (p pointer, i int, l long, f float, s ConvShape by value)."""
+    t = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "s": ConvShape}
+    return [(n, t[k]) for n, k in (f.split(":") for f in spec.split())]
+
+
+# job records of the grouped entry points (include/yms.h)
+class ConvFwdJob(ctypes.Structure):
+    _fields_ = _fields("shape:s x:p x_ld:i x_off:i wpacked:p y:p y_ld:i y_off:i scale:p shift:p act:i "
+                       "res:p res_ld:i res_off:i stats:p")
+
+
+class ConvDgradJob(ctypes.Structure):
+    _fields_ = _fields("shape:s dz:p dz_ld:i dz_off:i wpacked_t:p dx:p dx_ld:i dx_off:i accumulate:i")
+
+
+class BnFinalizeJob(ctypes.Structure):
+    _fields_ = _fields("c:i stats:p rows:i stats_ld:i count:l gamma:p beta:p rmean:p rvar:p momentum:f eps:f "
+                       "mean_invstd:p mi_ld:i scale:p shift:p")
+
+
+class BnPassJob(ctypes.Structure):
+    _fields_ = _fields("npix:l c:i z:p z_ld:i z_off:i gy:p gy_ld:i gy_off:i scale:p shift:p mean_invstd:p coef:p "
+                       "act:i out:p out_ld:i out_off:i res:p res_ld:i res_off:i res_acc:i ws:p counter:p dbias:p")
+
+
+class BnBwdFinalizeJob(ctypes.Structure):
+    _fields_ = _fields("c:i ws:p rows:i count:l dgamma:p dbeta:p coef:p")
+
+
 _L = ctypes.c_long
 _F = ctypes.c_float
 _D = ctypes.c_double
@@ -71,6 +103,10 @@ _SIGS = {
     "yms_conv_dgrad": (_I, [_SP, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     "yms_conv_dgrad_bnred_rows": (_I, [_SP]),
     "yms_conv_dgrad_bnred": (_I, [_SP, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "yms_conv_fwd_group": (_I, [_I, _P, _P]),
+    "yms_conv_dgrad_group": (_I, [_I, _P, _P]),
+    "yms_conv_fwd_group_launches": (_I, [_I, _P]),
+    "yms_conv_dgrad_group_launches": (_I, [_I, _P]),
     "yms_conv_wgrad_ws_bytes": (_SZ, [_SP]),
     "yms_conv_wgrad": (_I, [_SP, _P, _I, _I, _P, _I, _I, _P, _SZ, _P, _I, _P]),
     "yms_bn_fold": (_I, [_I, _P, _P, _P, _P, _F, _P, _P, _P]),
@@ -85,6 +121,12 @@ _SIGS = {
     "yms_bn_act_bwd_reduce_finalize": (_I, [_I, _L, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P,
                                             _P, _P]),
     "yms_bias_bwd": (_I, [_I, _L, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "yms_bn_finalize_group": (_I, [_I, _P, _P]),
+    "yms_affine_act_group": (_I, [_I, _I, _P, _P]),
+    "yms_bn_act_bwd_reduce_group": (_I, [_I, _I, _P, _P]),
+    "yms_bn_act_bwd_finalize_group": (_I, [_I, _P, _P]),
+    "yms_bn_act_bwd_apply_group": (_I, [_I, _I, _P, _P]),
+    "yms_bias_bwd_group": (_I, [_I, _I, _P, _P]),
     "yms_sppf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "yms_sppf_pool_fwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "yms_sppf_pool_bwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
@@ -153,9 +195,17 @@ def check(status, what):
 _prof = None
 _CONV = ("yms_conv_fwd", "yms_conv_dgrad", "yms_conv_dgrad_bnred", "yms_conv_wgrad", "yms_conv_stem_fwd")
 _DW = ("yms_dwconv_fwd", "yms_dwconv_dgrad", "yms_dwconv_wgrad")
+# grouped entry points (njobs, job array right before the stream): priced as the sum of their members;
+# the BN-family ones are recorded under their solo names, the ones the benchmark's rooflines count
+# (the grouped convs keep their own yms_conv_* names)
+_GROUP_AS = {"yms_conv_fwd_group": "yms_conv_fwd", "yms_conv_dgrad_group": "yms_conv_dgrad",
+             "yms_affine_act_group": "yms_affine_act", "yms_bn_act_bwd_reduce_group": "yms_bn_act_bwd_reduce",
+             "yms_bn_act_bwd_apply_group": "yms_bn_act_bwd_apply", "yms_bn_finalize_group": "yms_bn_finalize",
+             "yms_bn_act_bwd_finalize_group": "yms_bn_act_bwd_finalize", "yms_bias_bwd_group": "yms_bias_bwd"}
 # launches whose hipStream_t is the last argument (status-returning entry points ending in a void*)
 # (host-only entry points whose last pointer is a host buffer are listed out explicitly)
-_HOST_ONLY = {"yms_map_accumulate", "yms_map_accumulate_coco", "yms_pack_job_init"}
+_HOST_ONLY = {"yms_map_accumulate", "yms_map_accumulate_coco", "yms_pack_job_init", "yms_conv_fwd_group_launches",
+              "yms_conv_dgrad_group_launches"}
 _STREAM_LAST = {n for n, (res, args) in _SIGS.items()
                 if res is _I and args and args[-1] is _P and n not in _HOST_ONLY}
 
@@ -171,6 +221,23 @@ def _work(name, args):
     """(algorithmic FLOPs, algorithmic HBM bytes) of one launch: every operand read or written once.
     Convs: input + output + weights (fp32 weight gradient); depthwise: the same with fp32 [C][k][k]
     weights (FLOPs = 2 n h w c k^2, VALU); BN / branch-sum elementwise passes: their streams."""
+    solo = _GROUP_AS.get(name)
+    if solo is not None:
+        fl = nb = 0
+        for j in args[-2][:args[-3]]:
+            if solo in _CONV:
+                a = (ctypes.pointer(j.shape),)
+            elif solo == "yms_affine_act":
+                a = (args[0], j.npix, j.c) + (None,) * 6 + (j.res,)
+            elif solo == "yms_bn_act_bwd_apply":
+                a = (args[0], j.npix, j.c) + (None,) * 14 + (j.res, None, None, j.res_acc)
+            elif solo == "yms_bn_act_bwd_reduce":
+                a = (args[0], j.npix, j.c)
+            else:
+                break
+            f, b = _work(solo, a)
+            fl, nb = fl + f, nb + b
+        return fl, nb
     if name in _CONV:
         sh = args[0].contents
         fl = 2 * sh.n * sh.ho * sh.wo * sh.cout * sh.cin * sh.k * sh.k
@@ -216,7 +283,7 @@ def call(name, *args):
     check(getattr(lib(), name)(*args), name)
     e.record(st)
     fl, nb = _work(name, args)
-    _prof.append((name, s, e, fl, nb))
+    _prof.append((name if name.startswith("yms_conv_") else _GROUP_AS.get(name, name), s, e, fl, nb))
 
 
 def profile_begin():

@@ -36,6 +36,10 @@ ALIGN = 256
 # bias gradients only, yms_bias_bwd)
 BN_MOMENTUM = 0.03   # components.py:73
 BN_EPS = 1e-3
+# Options.head_group when YMS_HEAD_GROUP is unset: the forward only.  Grouping the backward as well
+# shortens the head's main-stream span (1.76 -> 1.37 ms) but not the step, whose backward waits for the
+# side stream's weight gradients (16.82 vs 16.93 ms/step, profiles/r07_head_group_ab.txt)
+HEAD_GROUP_DEFAULT = 1
 
 
 def r8(c):
@@ -57,6 +61,9 @@ class Options:
     wgrad_tail_first: bool  # YMS_WGRAD_FIRST=0: no layer enqueues its weight gradient first (Plan)
     grad_inplace: bool      # YMS_GRAD_INPLACE=0: always copy the incoming output gradients (runner)
     wgrad_stream: bool      # YMS_WGRAD_STREAM=0: weight gradients and packs on the main stream (runner)
+    # YMS_HEAD_GROUP: the head's independent levels run stage by stage as grouped launches (HeadGroup):
+    # 0 off, 1 the forward only, 2 forward and backward
+    head_group: int
     # the library's process-wide direct-conv route (yms_conv_direct_set): it changes
     # yms_conv_stats_rows and yms_conv_dgrad_bnred_rows, which size the plan's scratch
     direct: int
@@ -67,9 +74,12 @@ def read_options():
     def on(name):
         return os.environ.get(name, "1") != "0"
 
+    hg = os.environ.get("YMS_HEAD_GROUP", str(HEAD_GROUP_DEFAULT))
+    if hg not in ("0", "1", "2"):
+        raise RuntimeError(f"yms: YMS_HEAD_GROUP={hg!r}: expected 0 (off), 1 (forward) or 2 (forward + backward)")
     return Options(stem=on("YMS_STEM"), head_fuse=on("YMS_HEAD_FUSE"), bnred=on("YMS_BNRED"),
                    wgrad_tail_first=on("YMS_WGRAD_FIRST"), grad_inplace=on("YMS_GRAD_INPLACE"),
-                   wgrad_stream=on("YMS_WGRAD_STREAM"), direct=L.lib().yms_conv_direct_set(-1))
+                   wgrad_stream=on("YMS_WGRAD_STREAM"), head_group=int(hg), direct=L.lib().yms_conv_direct_set(-1))
 
 
 class Buf:
@@ -849,6 +859,203 @@ class SppfPoolOp(Op):
                rt.g(v), v.buf.ld, v.off, rt.gbase + rt.plan.gscratch["sppf"], rt.st)
 
 
+def _op_views(op):
+    """Every View an op holds, a SiblingConvOp's members' included."""
+    for k, v in vars(op).items():
+        for u in (v if isinstance(v, (list, tuple)) else (v,)):
+            if isinstance(u, View):
+                yield u
+            elif k == "members":
+                yield from _op_views(u)
+
+
+def _array(jobs):
+    return (type(jobs[0]) * len(jobs))(*jobs)
+
+
+class HeadGroup:
+    """Independent chains of conv ops -- the detection head's three levels (Builder.independent_chains)
+    -- run stage by stage: stage d holds, from every chain, the ops d steps behind their chain's input,
+    and each pass of a stage over its members is ONE grouped call (yms_*_group), in which every
+    member is decomposed exactly as by its solo call, so results are bit-identical to running the ops
+    one after the other.  Forward: the convs, then the BN finalizes, then the affine passes.  Backward:
+    the bias / BN reduce, finalize and apply passes, the input gradients, then each member's weight
+    gradient on the side stream, in the members' backward order, after the launch that wrote its dz.
+    The members' slices of the shared "stats", "bwd" and "coef" scratch are disjoint (layout).
+    The plan keeps the member ops in plan.ops; plan.sched runs the group in their place."""
+
+    KINDS = None    # the op types a group can run (set below the class)
+
+    def __init__(self, chains):
+        self.ops = [op for ch in chains for op in ch]
+        self.bwd_ops = tuple(reversed(self.ops))
+        depth = {}
+        for ch in chains:
+            for i, op in enumerate(ch):
+                depth[id(op)] = 1 + max((depth[id(q)] for q in ch[:i] if _overlap(q.y, op.x)), default=-1)
+        self.stages = [[op for op in self.ops if depth[id(op)] == d] for d in range(1 + max(depth.values()))]
+
+    @classmethod
+    def build(cls, chains):
+        """-> a HeadGroup, or None (every op then runs on its own, as without grouping) unless the
+        chains have the same sequence of op kinds, every op is a plain conv kind without a fused
+        neighbour (stem, producer's BN reduce, weight gradient first), ops of different chains touch
+        no common memory and no two outputs of one stage overlap."""
+        if len(chains) < 2 or len({tuple(type(op) for op in ch) for ch in chains}) != 1:
+            return None
+        for ch in chains:
+            for op in ch:
+                if type(op) not in cls.KINDS or op.stem_input is not None or op.tail_wgrad_first:
+                    return None
+                if getattr(op, "bnred_for", None) is not None or getattr(op, "bnred_by", None) is not None:
+                    return None
+        views = [[v for op in ch for v in _op_views(op)] for ch in chains]
+        for i, va in enumerate(views):
+            for vb in views[i + 1:]:
+                if any(_overlap(a, b) for a in va for b in vb):
+                    return None
+        g = cls(chains)
+        for st in g.stages:
+            if any(_overlap(a.y, b.y) for i, a in enumerate(st) for b in st[i + 1:]):
+                return None
+        return g
+
+    def layout(self, plan):
+        """Training: per stage, the members' slices of the shared scratch regions, which are sized by
+        the largest stage's sum."""
+        if not plan.training:
+            return
+        for st in self.stages:
+            stats = bwd = coef = 0
+            for op in st:
+                if isinstance(op, BiasConvOp):
+                    op.g_bwd = bwd
+                    bwd += _al(4 * 2 * op.c * L.lib().yms_bn_bwd_rows(op.npix, op.c))
+                    continue
+                for m, _ in op.parts():
+                    m.g_stats = stats
+                    stats += _al(4 * m.stats_rows * (2 * m.stats_ld + 1))
+                op.g_bwd, op.g_coef = bwd, coef
+                bwd += _al(4 * 2 * op.c * op.bwd_rows)
+                coef += _al(8 * op.c)
+            plan.need_scratch("stats", stats)
+            plan.need_scratch("bwd", bwd)
+            plan.need_scratch("coef", coef)
+
+    # ---- forward -------------------------------------------------------------------------
+    def fwd(self, rt):
+        if rt.training and not rt.prepacked:
+            for op in self.ops:
+                op.fwd(rt)
+            return
+        for st in self.stages:
+            self.fwd_stage(rt, st)
+
+    @staticmethod
+    def conv_job(m, rt, wp, out, ld, off, sc, sh, act, res, stats):
+        x = m.x
+        return L.ConvFwdJob(m.shape, rt.a(x), x.buf.ld, x.off, wp, out, ld, off, sc, sh, act, *_opt(rt.a, res), stats)
+
+    def fwd_stage(self, rt, st):
+        base, eb, dt = rt.base, rt.eval_base, rt.plan.dt
+        convs, fins, affs = [], [], []
+        for op in st:
+            y = op.y
+            if isinstance(op, BiasConvOp):
+                wp = base + op.t_wp if rt.training else eb + op.e_wp
+                convs.append(self.conv_job(op, rt, wp, rt.a(y), y.buf.ld, y.off, None, op.conv.bias.data_ptr(),
+                                           L.ACT_NONE, None, None))
+            elif not rt.training:
+                for m in (op.members if isinstance(op, SiblingConvOp) else (op,)):
+                    convs.append(self.conv_job(m, rt, eb + m.e_wp, rt.a(m.y), m.y.buf.ld, m.y.off, eb + m.e_sc,
+                                               eb + m.e_sh, m.act, m.res, None))
+            else:
+                z, sc, sh, mi = base + op.z, base + op.sc, base + op.sh, base + op.mi
+                for m, off in op.parts():
+                    stats = base + rt.plan.scratch["stats"] + m.g_stats
+                    convs.append(self.conv_job(m, rt, base + m.t_wp, z, op.zld, off, None, None, L.ACT_NONE, None, stats))
+                    bn = m.mod.bn
+                    fins.append(L.BnFinalizeJob(m.c, stats, m.stats_rows, m.stats_ld, op.npix, bn.weight.data_ptr(),
+                                                bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                                bn.running_var.data_ptr(),
+                                                bn.momentum if bn.momentum is not None else BN_MOMENTUM, bn.eps,
+                                                mi + 4 * off, op.c, sc + 4 * off, sh + 4 * off))
+                affs.append(L.BnPassJob(npix=op.npix, c=op.c, z=z, z_ld=op.zld, z_off=0, scale=sc, shift=sh,
+                                        act=op.act, out=rt.a(y), out_ld=y.buf.ld, out_off=y.off,
+                                        **dict(zip(("res", "res_ld", "res_off"), _opt(rt.a, op.res)))))
+        L.call("yms_conv_fwd_group", len(convs), _array(convs), rt.st)
+        if fins:
+            L.call("yms_bn_finalize_group", len(fins), _array(fins), rt.st)
+            L.call("yms_affine_act_group", dt, len(affs), _array(affs), rt.st)
+
+    # ---- backward ------------------------------------------------------------------------
+    def bwd_grouped(self, rt):
+        """The grouped backward serves the case every training step meets: all the members' parameters
+        take a gradient and each sibling pair's gradients are adjacent in the flat arena.  Otherwise
+        (a frozen member), and with Options.head_group < 2, the members run their own backward."""
+        if rt.plan.opts.head_group < 2:
+            return False
+        for op in self.ops:
+            if any(rt.pgrad(pi) is None for pi in op.grad_params()):
+                return False
+            if isinstance(op, SiblingConvOp) and any(op._adjacent(rt, a) is None for a in ("pg", "pb", "pw")):
+                return False
+        return True
+
+    def bwd(self, rt):
+        if not self.bwd_grouped(rt):
+            for op in self.bwd_ops:
+                op.bwd(rt)
+            return
+        for st in reversed(self.stages):
+            self.bwd_stage(rt, st[::-1])
+
+    def bwd_stage(self, rt, ops):
+        base, gb, gs, dt = rt.base, rt.gbase, rt.plan.gscratch, rt.plan.dt
+        dzs = {}      # op -> (address, channel stride, channel offset) of its output gradient dz
+        bias, red, fin, app = [], [], [], []
+        for op in ops:
+            y = op.y
+            gy, gyl, gyo = rt.g(y), y.buf.ld, y.off
+            ws = gb + gs["bwd"] + op.g_bwd
+            if isinstance(op, BiasConvOp):
+                bias.append(L.BnPassJob(npix=op.npix, c=op.c, gy=gy, gy_ld=gyl, gy_off=gyo, ws=ws,
+                                        counter=rt.cnt(op.cnt), dbias=rt.pgrad(op.pbias)))
+                dzs[id(op)] = (gy, gyl, gyo)
+                continue
+            z, coef = base + op.z, gb + gs["coef"] + op.g_coef
+            common = dict(npix=op.npix, c=op.c, z=z, z_ld=op.zld, z_off=0, gy=gy, gy_ld=gyl, gy_off=gyo,
+                          scale=base + op.sc, shift=base + op.sh, mean_invstd=base + op.mi, act=op.act)
+            red.append(L.BnPassJob(ws=ws, **common))
+            if isinstance(op, SiblingConvOp):
+                dg, db = op._adjacent(rt, "pg"), op._adjacent(rt, "pb")
+            else:
+                dg, db = rt.pgrad(op.pg), rt.pgrad(op.pb)
+            fin.append(L.BnBwdFinalizeJob(op.c, ws, op.bwd_rows, op.npix, dg, db, coef))
+            res, res_ld, res_off = _opt(rt.g, op.res)
+            app.append(L.BnPassJob(coef=coef, out=z, out_ld=op.zld, out_off=0, res=res, res_ld=res_ld,
+                                   res_off=res_off, res_acc=op.acc_res, **common))
+            dzs[id(op)] = (z, op.zld, 0)
+        if bias:
+            L.call("yms_bias_bwd_group", dt, len(bias), _array(bias), rt.st)
+        if red:
+            L.call("yms_bn_act_bwd_reduce_group", dt, len(red), _array(red), rt.st)
+            L.call("yms_bn_act_bwd_finalize_group", len(fin), _array(fin), rt.st)
+            L.call("yms_bn_act_bwd_apply_group", dt, len(app), _array(app), rt.st)
+        dgs = []
+        for op in ops:
+            x = op.x
+            if x.buf.needs_grad:
+                dgs.append(L.ConvDgradJob(op.shape, *dzs[id(op)], base + op.t_wpt, rt.g(x), x.buf.ld, x.off, op.acc_x))
+        if dgs:
+            L.call("yms_conv_dgrad_group", len(dgs), _array(dgs), rt.st)
+        for op in ops:
+            op.wgrad(rt, *dzs[id(op)])
+
+
+HeadGroup.KINDS = (ConvOp, SiblingConvOp, BiasConvOp)
+
+
 class Builder:
     """Collects buffers, ops and parameter references while modules ``emit``."""
 
@@ -859,6 +1066,7 @@ class Builder:
         self.bufs = []
         self.ops = []
         self.param_refs = []      # (module, attr)
+        self.chain_sets = []      # independent_chains: [(first op index, end), ...] per set
         self._pidx = {}
 
     def new(self, h, w, c, name="act", ld=None):
@@ -911,6 +1119,12 @@ class Builder:
         self.ops.append(op)
         return [m.y for m in op.members]
 
+    def independent_chains(self, ranges):
+        """The ops emitted in each (first, end) index range of self.ops form a chain that shares no
+        memory with the other ranges' (the head's levels): the plan may run them side by side, stage
+        by stage (HeadGroup)."""
+        self.chain_sets.append([tuple(r) for r in ranges])
+
     def add(self, a, b, out=None):
         """y = a + b (b may be None: a placement copy) -> view."""
         if b is not None and (a.h, a.w, a.c) != (b.h, b.w, b.c):
@@ -958,6 +1172,7 @@ class Plan:
                 if type(op) is ConvOp and op.x.buf.idx in stem_out:
                     op.tail_wgrad_first = True
         self._find_bnred()
+        self.groups = self._find_groups(b.chain_sets)
         La, Le = Layout(), Layout()
         # an input the stem conv reads as NCHW fp32 has no NHWC buffer: no arena bytes, and no
         # per-step zeroing of its padding channels (3 -> 8: 419 MB, 51 us per configs[2] step)
@@ -970,6 +1185,8 @@ class Plan:
         self.act_bytes = La.size
         for op in self.ops:
             op.layout(self, La, Le)
+        for g in self.groups:
+            g.layout(self)
         self.scratch = {}
         if self.training:
             self.scratch["stats"] = La.alloc(self.scratch_req.get("stats", 0))
@@ -1078,6 +1295,23 @@ class Plan:
             c.bnred_for, c.bnred_wkey = q, key
             q.bnred_by, q.bnred_key, q.bnred_rows = c, key, rows
             self.need_scratch(key, 4 * rows * 2 * r8(x.c))
+
+    def _find_groups(self, chain_sets):
+        """The HeadGroups of the builder's chain sets (Options.head_group; a set whose ranges are not
+        one contiguous run of ops, or that HeadGroup.build declines, stays ungrouped), and self.sched:
+        what the runner walks -- the ops, with each group in the place of its members."""
+        groups = []
+        if self.opts.head_group:
+            for ranges in chain_sets:
+                if any(a >= b for a, b in ranges) or any(r[1] != q[0] for r, q in zip(ranges, ranges[1:])):
+                    continue
+                g = HeadGroup.build([self.ops[a:b] for a, b in ranges])
+                if g is not None:
+                    groups.append(g)
+        first = {id(g.ops[0]): g for g in groups}
+        member = {id(op) for g in groups for op in g.ops}
+        self.sched = [first.get(id(op), op) for op in self.ops if id(op) in first or id(op) not in member]
+        return groups
 
     def counter(self):
         """Reserve one 16-B arrival counter in the grad scratch (-> its index)."""

@@ -151,7 +151,7 @@ class _PlanFn(torch.autograd.Function):
         arena = plan.new_arena(dev, stream)
         rt = Rt(plan, arena.data_ptr(), stream, True)
         _load_inputs(plan, rt, inputs)
-        ops = plan.ops
+        ops = plan.sched
         if plan.opts.wgrad_stream and plan.ops and plan.ops[0] in plan.stem_inputs.values():
             # the stem conv reads the fp32 weight itself: the step's weight packs go to the side
             # stream and overlap it; every later conv is ordered after them
@@ -235,19 +235,21 @@ class _PlanFn(torch.autograd.Function):
         if hook is not None:
             views = param_views()
             hook.begin(plan, pg, ptrs, views)
-        for op in reversed(plan.ops):
-            op.bwd(rt)
-            if hook is not None and hook.pending(op):
-                if rt.side is not None:
-                    # the bucket's dw come from side-stream wgrads and its BN/bias grads from the main
-                    # stream: order the side stream after main and issue the collective from the side
-                    # stream, so the main stream never stalls on the wgrads (the collective's stream
-                    # waits on the side stream; finish() joins main to the collectives)
-                    rt.side.wait_stream(rt.main)
-                    with torch.cuda.stream(rt.side):
+        for step in reversed(plan.sched):
+            step.bwd(rt)
+            # (a HeadGroup finishes all its member ops together: their buckets go out after it)
+            for op in getattr(step, "bwd_ops", (step,)):
+                if hook is not None and hook.pending(op):
+                    if rt.side is not None:
+                        # the bucket's dw come from side-stream wgrads and its BN/bias grads from the main
+                        # stream: order the side stream after main and issue the collective from the side
+                        # stream, so the main stream never stalls on the wgrads (the collective's stream
+                        # waits on the side stream; finish() joins main to the collectives)
+                        rt.side.wait_stream(rt.main)
+                        with torch.cuda.stream(rt.side):
+                            hook.op_done(op)
+                    else:
                         hook.op_done(op)
-                else:
-                    hook.op_done(op)
         if rt.side is not None:
             rt.main.wait_stream(rt.side)
             rt.side = None
@@ -314,7 +316,7 @@ def run(module, inputs, grad_hook=None):
         rt = Rt(plan, arena.data_ptr(), stream, False)
         rt.eval_base = plan.ensure_eval_cache(dev, stream)
         _load_inputs(plan, rt, inputs)
-        for op in plan.ops:
+        for op in plan.sched:
             op.fwd(rt)
         if decode:
             return plan, [_decode(plan, rt, arena)]

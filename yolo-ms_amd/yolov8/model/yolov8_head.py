@@ -44,8 +44,9 @@ class Head(_YmsModule):
     def emit(self, b, x0, x1, x2):
         if self.ch != 16:
             raise RuntimeError("yms: the DFL decode is built for ch=16 (as the reference's DFL())")
-        outs = []
+        outs, levels = [], []
         for i, x in enumerate((x0, x1, x2)):
+            first = len(b.ops)
             o = b.new(x.h, x.w, self.no, name=f"head_out{i}")
             # the two branches' first convs read the same x_i: one SiblingConvOp (one buffer
             # [box | cls], one BN backward pass, one input and one weight gradient for both)
@@ -55,6 +56,9 @@ class Head(_YmsModule):
                 t = br[1].emit(b, t)
                 b.conv2d_bias(br[2], t, out=o.slot(off, c))
             outs.append(o)
+            levels.append((first, len(b.ops)))
+        # the levels depend on nothing in each other: the plan may run them as grouped launches
+        b.independent_chains(levels)
         return outs
 
     def yms_decode_info(self):
