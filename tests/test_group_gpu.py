@@ -76,8 +76,7 @@ class FwdCase:
             L.call("yms_conv_fwd_group", len(jobs), _arr(jobs), L.stream_ptr())
         else:
             for j in jobs:
-                L.call("yms_conv_fwd", ctypes.pointer(j.shape), j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off,
-                       j.scale, j.shift, j.act, j.res, j.res_ld, j.res_off, j.stats, L.stream_ptr())
+                L.call_job("yms_conv_fwd", j, L.stream_ptr())
         torch.cuda.synchronize()
         return outs
 
@@ -157,8 +156,7 @@ class DgradCase:
             L.call("yms_conv_dgrad_group", len(jobs), _arr(jobs), L.stream_ptr())
         else:
             for j in jobs:
-                L.call("yms_conv_dgrad", ctypes.pointer(j.shape), j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld,
-                       j.dx_off, j.accumulate, L.stream_ptr())
+                L.call_job("yms_conv_dgrad", j, L.stream_ptr())
         torch.cuda.synchronize()
         return outs
 
@@ -232,9 +230,7 @@ def test_bn_finalize_group_equals_solo(cs):
             L.call("yms_bn_finalize_group", len(jobs), _arr(jobs), L.stream_ptr())
         else:
             for j in jobs:
-                L.call("yms_bn_finalize_ld", j.c, j.stats, j.rows, j.stats_ld, j.count, j.gamma, j.beta, j.rmean, j.rvar,
-                       ctypes.c_float(j.momentum), ctypes.c_float(j.eps), j.mean_invstd, j.mi_ld, j.scale, j.shift,
-                       L.stream_ptr())
+                L.call_job("yms_bn_finalize_ld", j, L.stream_ptr())
         torch.cuda.synchronize()
         return outs
 
@@ -271,8 +267,7 @@ def test_bn_pass_groups_equal_solo(cs, dt):
             L.call("yms_affine_act_group", code, len(jobs), _arr(jobs), st)
         else:
             for j in jobs:
-                L.call("yms_affine_act", code, j.npix, j.c, j.z, j.z_ld, j.z_off, j.scale, j.shift, j.act, j.res, j.res_ld,
-                       j.res_off, j.out, j.out_ld, j.out_off, st)
+                L.call_job("yms_affine_act", j, st, code)
         torch.cuda.synchronize()
         return outs
 
@@ -302,14 +297,11 @@ def test_bn_pass_groups_equal_solo(cs, dt):
             L.call("yms_bn_act_bwd_apply_group", code, len(app), _arr(app), st)
         else:
             for j in red:
-                L.call("yms_bn_act_bwd_reduce", code, j.npix, j.c, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale,
-                       j.shift, j.mean_invstd, j.act, j.ws, st)
+                L.call_job("yms_bn_act_bwd_reduce", j, st, code)
             for j in fin:
-                L.call("yms_bn_act_bwd_finalize", j.c, j.ws, j.rows, j.count, j.dgamma, j.dbeta, j.coef, st)
+                L.call_job("yms_bn_act_bwd_finalize", j, st)
             for j in app:
-                L.call("yms_bn_act_bwd_apply", code, j.npix, j.c, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale,
-                       j.shift, j.mean_invstd, j.coef, j.act, j.out, j.out_ld, j.out_off, j.res, j.res_ld, j.res_off,
-                       j.res_acc, st)
+                L.call_job("yms_bn_act_bwd_apply", j, st, code)
         torch.cuda.synchronize()
         return outs
 
@@ -332,7 +324,7 @@ def test_bn_pass_groups_equal_solo(cs, dt):
             L.call("yms_bias_bwd_group", code, len(jobs), _arr(jobs), st)
         else:
             for j in jobs:
-                L.call("yms_bias_bwd", code, j.npix, j.c, j.gy, j.gy_ld, j.gy_off, j.ws, j.counter, j.dbias, st)
+                L.call_job("yms_bias_bwd", j, st, code)
         torch.cuda.synchronize()
         assert int(cnt.abs().sum()) == 0          # every member's arrival counter is back at zero
         return outs
@@ -359,8 +351,7 @@ def test_bn_group_sizes():
                 L.call("yms_affine_act_group", L.BF16, n, _arr(jobs), L.stream_ptr())
             else:
                 for j in jobs:
-                    L.call("yms_affine_act", L.BF16, j.npix, j.c, j.z, 64, 0, j.scale, j.shift, j.act, None, 0, 0, j.out, 64, 0,
-                           L.stream_ptr())
+                    L.call_job("yms_affine_act", j, L.stream_ptr(), L.BF16)
             torch.cuda.synchronize()
             res.append(ys)
         _same(*res)

@@ -27,5 +27,5 @@ for r in rows:
     n = n.replace("yms::", "").replace("(yms::NTParams)", "").replace("(yms::TTParams)", "")
     if flt and flt not in n:
         continue
-    print(f"{n[:88]:88s} v={r.get('VGPRs')} a={r.get('AGPRs')} scr={r.get('ScratchSize [bytes/lane]')} "
+    print(f"{n[:88]:88s} v={r.get('VGPRs')} a={r.get('AGPRs')} s={r.get('TotalSGPRs')} scr={r.get('ScratchSize [bytes/lane]')} "
           f"occ={r.get('Occupancy [waves/SIMD]')} lds={r.get('LDS Size [bytes/block]')}")

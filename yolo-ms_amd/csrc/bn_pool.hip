@@ -1085,40 +1085,99 @@ yms_status yms_bn_fold(int c, const float* gamma, const float* beta, const float
   return launch_status();
 }
 
-yms_status yms_bn_finalize_ld(int c, float* stats, int rows, int stats_ld, long count,
-                              const float* gamma, const float* beta, float* rmean, float* rvar,
-                              float momentum, float eps, float* mean_invstd, int mi_ld, float* scale,
-                              float* shift, void* stream) {
-  if (c <= 0 || !stats || rows <= 0 || count <= 0 || !gamma || !beta || !mean_invstd || !scale || !shift)
-    return YMS_ERR_INVALID;
-  if (stats_ld < c || mi_ld < c) return YMS_ERR_INVALID;
-  int rs = 1, nrows = rows;
-  if (rows > 1024) {   // long tables: pre-reduce in parallel (in place), then finalize the partial rows
-    const int S = std::min(256, cdiv(rows, 64));
-    rs = cdiv(rows, S);
-    nrows = cdiv(rows, rs);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(cdiv(c, 64), nrows), dim3(256), 0, (hipStream_t)stream, c,
-                       stats, rows, stats_ld, rs);
-  }
-  if (rs == 1) {
-    hipLaunchKernelGGL(bn_finalize_small_kernel, dim3(cdiv(c, 8)), dim3(256), 0, (hipStream_t)stream, c,
-                       (const float*)stats, rows, stats_ld, count, gamma, beta, rmean, rvar, momentum, eps,
-                       mean_invstd, mi_ld, scale, shift);
-    return launch_status();
-  }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(c, FIN_CW)), dim3(1024), 0, (hipStream_t)stream, c,
-                     (const float*)stats, nrows, stats_ld, rs, rows, count, gamma, beta, rmean, rvar, momentum,
-                     eps, mean_invstd, mi_ld, scale, shift);
-  return launch_status();
+}  // extern "C"
+
+// ---- the BN / bias passes ---------------------------------------------------------------------
+// Each pass is described ONCE, over its public job record (include/yms.h): check (validation), groupable
+// (does the grouped kernel serve this job), blocks and dev (block count and device-side job, from one
+// pixels-per-block formula), launch_solo and launch_group.  run_pass runs a pass over n jobs; a solo
+// entry point is a job literal and run_pass with n = 1.
+static unsigned pix_blocks(long npix, long ppb) { return (unsigned)((npix + ppb - 1) / ppb); }
+
+static PassJob pass_job(const yms_bn_pass_job& j, long ppb) {
+  return PassJob{j.npix, ppb, j.c, j.act, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale, j.shift,
+                 j.mean_invstd, j.coef, j.out, j.out_ld, j.out_off, j.res, j.res_ld, j.res_off, j.res_acc, j.ws};
 }
 
-yms_status yms_bn_finalize(int c, float* stats, int rows, int stats_ld, long count,
-                           const float* gamma, const float* beta, float* rmean, float* rvar,
-                           float momentum, float eps, float* mean_invstd, float* scale,
-                           float* shift, void* stream) {
-  return yms_bn_finalize_ld(c, stats, rows, stats_ld, count, gamma, beta, rmean, rvar, momentum, eps,
-                            mean_invstd, c, scale, shift, stream);
+// The jobs the grouped kernel serves go out BN_GROUP_MAX per launch, each member with its solo launch's
+// block count and per-block ranges; a job alone, or one the grouped kernel does not serve, takes the
+// solo launch, in job order after the grouped launches.  Every job is checked before the first launch.
+template <typename P>
+static yms_status run_pass(int dtype, int njobs, const typename P::Job* jobs, void* stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (njobs == 1) {                           // the solo entry points: no partition, nothing allocated
+    const yms_status e = P::check(jobs[0]);
+    return e ? e : P::launch_solo(dtype, jobs[0], st);
+  }
+  std::vector<int> idx;
+  for (int i = 0; i < njobs; ++i) {
+    if (yms_status e = P::check(jobs[i])) return e;
+    if (P::groupable(jobs[i])) idx.push_back(i);
+  }
+  std::vector<char> grouped(njobs, 0);
+  if (idx.size() >= 2) {
+    for (size_t i = 0; i < idx.size(); i += BN_GROUP_MAX) {
+      const int n = (int)std::min<size_t>(BN_GROUP_MAX, idx.size() - i);
+      if (n < 2) break;                      // a lone remainder: solo
+      BnGroup<typename P::Dev> g{};
+      g.n = n;
+      for (int k = 0; k < n; ++k) {
+        const typename P::Job& j = jobs[idx[i + k]];
+        g.job[k] = P::dev(j);
+        g.first[k + 1] = g.first[k] + P::blocks(j);
+        grouped[idx[i + k]] = 1;
+      }
+      if (yms_status e = P::launch_group(dtype, g, g.first[n], st)) return e;
+      if (yms_status e = launch_status()) return e;
+    }
+  }
+  for (int i = 0; i < njobs; ++i)
+    if (!grouped[i])
+      if (yms_status e = P::launch_solo(dtype, jobs[i], st)) return e;
+  return YMS_OK;
 }
+
+struct FinalizePass {                        // forward: statistics rows -> mean / invstd, scale / shift, running stats
+  using Job = yms_bn_finalize_job;
+  using Dev = FinJob;
+  static yms_status check(const Job& j) {
+    if (j.c <= 0 || !j.stats || j.rows <= 0 || j.count <= 0 || !j.gamma || !j.beta || !j.mean_invstd || !j.scale ||
+        !j.shift)
+      return YMS_ERR_INVALID;
+    return j.stats_ld < j.c || j.mi_ld < j.c ? YMS_ERR_INVALID : YMS_OK;
+  }
+  static bool groupable(const Job& j) { return j.rows <= 1024; }   // long tables: launch_solo's pre-reduction
+  static unsigned blocks(const Job& j) { return (unsigned)cdiv(j.c, 8); }
+  static Dev dev(const Job& j) {
+    return FinJob{j.c, j.rows, j.stats_ld, j.mi_ld, j.stats, j.count, j.gamma, j.beta, j.rmean, j.rvar,
+                  j.momentum, j.eps, j.mean_invstd, j.scale, j.shift};
+  }
+  static yms_status launch_solo(int, const Job& j, hipStream_t st) {
+    int rs = 1, nrows = j.rows;
+    if (j.rows > 1024) {   // long tables: pre-reduce in parallel (in place), then finalize the partial rows
+      const int S = std::min(256, cdiv(j.rows, 64));
+      rs = cdiv(j.rows, S);
+      nrows = cdiv(j.rows, rs);
+      hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(cdiv(j.c, 64), nrows), dim3(256), 0, st, j.c, j.stats, j.rows,
+                         j.stats_ld, rs);
+    }
+    if (rs == 1) {
+      hipLaunchKernelGGL(bn_finalize_small_kernel, dim3(blocks(j)), dim3(256), 0, st, j.c, (const float*)j.stats,
+                         j.rows, j.stats_ld, j.count, j.gamma, j.beta, j.rmean, j.rvar, j.momentum, j.eps,
+                         j.mean_invstd, j.mi_ld, j.scale, j.shift);
+      return launch_status();
+    }
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(j.c, FIN_CW)), dim3(1024), 0, st, j.c, (const float*)j.stats,
+                       nrows, j.stats_ld, rs, j.rows, j.count, j.gamma, j.beta, j.rmean, j.rvar, j.momentum, j.eps,
+                       j.mean_invstd, j.mi_ld, j.scale, j.shift);
+    return launch_status();
+  }
+  static yms_status launch_group(int, const BnGroup<Dev>& g, unsigned nb, hipStream_t st) {
+    hipLaunchKernelGGL(bn_finalize_small_group_kernel, dim3(nb), dim3(256), 0, st, g);
+    return YMS_OK;
+  }
+};
 
 // pixels per block for the channel-stationary kernels: about four U-pixel iterations per
 // thread (amortises the per-channel parameter loads; measured best of 1/2/4/8), at most 8192
@@ -1129,28 +1188,6 @@ static long elem_ppb(long npix, int c, int iters = 4) {
   // (round 3: a floor of 1024-2048 blocks for the small 20^2 / 40^2 layers made the step slower,
   // profiles/r03s_bn_minblocks_ab.txt: the extra blocks wait for CU slots the side stream holds)
   return (npix + blocks - 1) / blocks;
-}
-
-yms_status yms_affine_act(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
-                          const float* scale, const float* shift, int act,
-                          const void* res, int res_ld, int res_off,
-                          void* y, int y_ld, int y_off, void* stream) {
-  if (npix <= 0 || !z || !y || !vok(z_ld, z_off, c) || !vok(y_ld, y_off, c)) return YMS_ERR_INVALID;
-  if (res && !vok(res_ld, res_off, c)) return YMS_ERR_INVALID;
-  if (c > 2048) return YMS_ERR_UNSUPPORTED;
-  // two U-pixel iterations per thread: the forward affine pass (no side-stream work beside it) took
-  // 1.73 / 1.74 ms per YOLOv8-s step against 1.80 / 1.80 at four, 3.66-3.68 vs 3.70-3.73 ms on
-  // YOLO-MS-S (interleaved, profiles/r03y_affine_iters_ab.txt)
-  // software-pipelined loop: affine 1.72 -> 1.70 ms per YOLOv8-s step, 3.68 -> 3.57 ms on YOLO-MS-S,
-  // steps 18.20 -> 18.13 ms and 37.24 -> 37.12 ms over the serial loop (interleaved pairs; pipelined
-  // at 4 / 8 iterations slower, profiles/r03zg_affine_pipe_ab.txt)
-  const long ppb = elem_ppb(npix, c, 2);
-  const unsigned blocks = (unsigned)((npix + ppb - 1) / ppb);
-  YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((affine_act_kernel<T, true>), dim3(blocks), dim3(256), 0,
-                                               (hipStream_t)stream, npix, c, (const T*)z, z_ld, z_off,
-                                               scale, shift, act, (const T*)res, res_ld, res_off, (T*)y,
-                                               y_ld, y_off, ppb));
-  return launch_status();
 }
 
 // pixels per BN-backward reduce block.  Partial-sum rows = reduce blocks, at most 256 with the
@@ -1167,49 +1204,220 @@ static long bwd_pix_per_block(long npix, int c, bool fused) {
   return (npix + rows - 1) / rows;
 }
 
+// The per-pixel passes over yms_bn_pass_job: PPB is the pass's pixels-per-block formula, the one place
+// the block count and the per-block pixel ranges of a job, solo or grouped, come from.
+template <long (*PPB)(const yms_bn_pass_job&)>
+struct PixelPass {
+  using Job = yms_bn_pass_job;
+  using Dev = PassJob;
+  static bool groupable(const Job&) { return true; }
+  static unsigned blocks(const Job& j) { return pix_blocks(j.npix, PPB(j)); }
+  static Dev dev(const Job& j) { return pass_job(j, PPB(j)); }
+};
+
+// two U-pixel iterations per thread: the forward affine pass (no side-stream work beside it) took
+// 1.73 / 1.74 ms per YOLOv8-s step against 1.80 / 1.80 at four, 3.66-3.68 vs 3.70-3.73 ms on
+// YOLO-MS-S (interleaved, profiles/r03y_affine_iters_ab.txt)
+// software-pipelined loop: affine 1.72 -> 1.70 ms per YOLOv8-s step, 3.68 -> 3.57 ms on YOLO-MS-S,
+// steps 18.20 -> 18.13 ms and 37.24 -> 37.12 ms over the serial loop (interleaved pairs; pipelined
+// at 4 / 8 iterations slower, profiles/r03zg_affine_pipe_ab.txt)
+static long affine_ppb(const yms_bn_pass_job& j) { return elem_ppb(j.npix, j.c, 2); }
+
+struct AffinePass : PixelPass<affine_ppb> {  // y = act(z*scale + shift) (+ res)
+  static yms_status check(const Job& j) {
+    if (j.npix <= 0 || !j.z || !j.out || !vok(j.z_ld, j.z_off, j.c) || !vok(j.out_ld, j.out_off, j.c))
+      return YMS_ERR_INVALID;
+    if (j.res && !vok(j.res_ld, j.res_off, j.c)) return YMS_ERR_INVALID;
+    return j.c > 2048 ? YMS_ERR_UNSUPPORTED : YMS_OK;
+  }
+  static yms_status launch_solo(int dtype, const Job& j, hipStream_t st) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((affine_act_kernel<T, true>), dim3(blocks(j)), dim3(256), 0, st,
+                                                 j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, j.scale, j.shift, j.act,
+                                                 (const T*)j.res, j.res_ld, j.res_off, (T*)j.out, j.out_ld, j.out_off,
+                                                 affine_ppb(j)));
+    return launch_status();
+  }
+  static yms_status launch_group(int dtype, const BnGroup<Dev>& g, unsigned nb, hipStream_t st) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((affine_act_group_kernel<T, true>), dim3(nb), dim3(256), 0, st, g));
+    return YMS_OK;
+  }
+};
+
+// gy (and z) -> partial rows: the validation the reduce, the fused reduce + finalize and the bias
+// reduce share (with_z: the BN + act reduce; fused: the in-launch finalize's arrival counter)
+static yms_status reduce_check(const yms_bn_pass_job& j, bool with_z, bool fused) {
+  if (j.npix <= 0 || !j.gy || !j.ws || (fused && !j.counter) || !vok(j.gy_ld, j.gy_off, j.c)) return YMS_ERR_INVALID;
+  if (with_z && (!vok(j.z_ld, j.z_off, j.c) || !j.scale || !j.shift || !j.mean_invstd)) return YMS_ERR_INVALID;
+  return j.c > 2048 ? YMS_ERR_UNSUPPORTED : YMS_OK;
+}
+
+static long reduce_ppb(const yms_bn_pass_job& j) { return bwd_pix_per_block(j.npix, j.c, false); }
+
+struct ReducePass : PixelPass<reduce_ppb> {  // backward: partial sums of da and da*xhat -> ws
+  static yms_status check(const Job& j) { return reduce_check(j, j.z != nullptr, false); }
+  static bool groupable(const Job& j) { return j.z != nullptr; }   // the plain column sum: solo
+  static yms_status launch_solo(int dtype, const Job& j, hipStream_t st) {
+    // software-pipelined loop (c % 8 == 0).  At 512 rows it was step-neutral over the serial loop
+    // (the reduce -10%, the apply after it +5%, profiles/r03zb_bn_reduce_pipe_ab.txt); with the
+    // latency hidden inside each block, half the blocks (256 rows, bwd_pix_per_block) win: YOLOv8-s
+    // 18.63 -> 18.32 ms/step, YOLO-MS-S 37.42 -> 37.28 ms (means of four interleaved runs each,
+    // profiles/r03zd_*, r03ze_*); serial at 256 rows is slower.
+#define YMS_RED(HZ)                                                                                                \
+  YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, HZ, false, true>), dim3(blocks(j)), dim3(256), \
+                                               0, st, j.npix, j.c, HZ ? (const T*)j.z : (const T*)nullptr,         \
+                                               HZ ? j.z_ld : 0, HZ ? j.z_off : 0, (const T*)j.gy, j.gy_ld, j.gy_off, \
+                                               j.scale, j.shift, j.mean_invstd, j.act, j.ws, reduce_ppb(j)))
+    if (j.z) YMS_RED(true);
+    else YMS_RED(false);
+#undef YMS_RED
+    return launch_status();
+  }
+  static yms_status launch_group(int dtype, const BnGroup<Dev>& g, unsigned nb, hipStream_t st) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(bn_bwd_reduce_group_kernel<T>, dim3(nb), dim3(256), 0, st, g));
+    return YMS_OK;
+  }
+};
+
+struct BwdFinalizePass {                     // backward: partial rows -> dgamma, dbeta, the apply's coefficients
+  using Job = yms_bn_bwd_finalize_job;
+  using Dev = BwdFinJob;
+  static yms_status check(const Job& j) {
+    return j.c <= 0 || !j.ws || j.rows <= 0 || j.count <= 0 ? YMS_ERR_INVALID : YMS_OK;
+  }
+  static bool groupable(const Job&) { return true; }
+  static unsigned blocks(const Job& j) { return (unsigned)cdiv(j.c, 32); }
+  static Dev dev(const Job& j) { return BwdFinJob{j.c, j.rows, j.ws, j.count, j.dgamma, j.dbeta, j.coef}; }
+  static yms_status launch_solo(int, const Job& j, hipStream_t st) {
+    // (tried and dropped: float4 channel quads x 32 row lanes with every load of a lane in flight --
+    // 19.42 -> 19.65 ms; a latency-shaped 8-channel x 32-lane variant with 4x the blocks -- +0.15-0.3
+    // ms, profiles/r03q_bn_finalize_ab.txt: inside the step the finalize waits for CU slots, not loads)
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<8>, dim3(blocks(j)), dim3(256), 0, st, j.c, j.ws, j.rows, j.count,
+                       j.dgamma, j.dbeta, j.coef);
+    return launch_status();
+  }
+  static yms_status launch_group(int, const BnGroup<Dev>& g, unsigned nb, hipStream_t st) {
+    hipLaunchKernelGGL(bn_bwd_finalize_group_kernel<8>, dim3(nb), dim3(256), 0, st, g);
+    return YMS_OK;
+  }
+};
+
+// software-pipelined loop at eight U-pixel iterations per thread (half the blocks of the serial
+// loop's best, four): YOLO-MS-S 37.27 -> 37.11 ms/step, YOLOv8-s 18.53 -> 18.49 ms (means of
+// two interleaved runs; 4 / 16 iterations pipelined are slower, profiles/r03zf_bn_apply_pipe_ab.txt)
+static long apply_ppb(const yms_bn_pass_job& j) {
+  return elem_ppb(j.npix, j.c, 8 * BN_U / BN_UA);    // the same pixels per block at any U
+}
+
+struct ApplyPass : PixelPass<apply_ppb> {    // backward: dz over z (+ the residual's gradient)
+  static yms_status check(const Job& j) {
+    if (j.npix <= 0 || !j.z || !j.gy || !j.out || !j.scale || !j.shift || !j.mean_invstd || !j.coef)
+      return YMS_ERR_INVALID;
+    if (!vok(j.z_ld, j.z_off, j.c) || !vok(j.gy_ld, j.gy_off, j.c) || !vok(j.out_ld, j.out_off, j.c))
+      return YMS_ERR_INVALID;
+    if (j.res && !vok(j.res_ld, j.res_off, j.c)) return YMS_ERR_INVALID;
+    return j.c > 2048 ? YMS_ERR_UNSUPPORTED : YMS_OK;
+  }
+  static yms_status launch_solo(int dtype, const Job& j, hipStream_t st) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(blocks(j)), dim3(256), 0, st,
+                                                 j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, (const T*)j.gy, j.gy_ld,
+                                                 j.gy_off, j.scale, j.shift, j.mean_invstd, j.coef, j.act, (T*)j.out,
+                                                 j.out_ld, j.out_off, (T*)j.res, j.res_ld, j.res_off, j.res_acc,
+                                                 apply_ppb(j)));
+    return launch_status();
+  }
+  static yms_status launch_group(int dtype, const BnGroup<Dev>& g, unsigned nb, hipStream_t st) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_apply_group_kernel<T, true>), dim3(nb), dim3(256), 0, st, g));
+    return YMS_OK;
+  }
+};
+
+// reduce + finalize in one launch (the last block to arrive sums the table): yms_bn_act_bwd_reduce_finalize,
+// and the bias pass, which is its z-less form
+static long fused_ppb(const yms_bn_pass_job& j) { return bwd_pix_per_block(j.npix, j.c, true); }
+
+static yms_status launch_reduce_finalize(int dtype, const yms_bn_pass_job& j, bool with_z, const BwdFin& fin,
+                                         hipStream_t st) {
+  const long ppb = fused_ppb(j);
+  const unsigned rows = pix_blocks(j.npix, ppb);
+  if (with_z) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, true>), dim3(rows), dim3(256), 0, st,
+                                                 j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, (const T*)j.gy, j.gy_ld,
+                                                 j.gy_off, j.scale, j.shift, j.mean_invstd, j.act, j.ws, ppb, fin));
+  } else {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, true>), dim3(rows), dim3(256), 0, st,
+                                                 j.npix, j.c, (const T*)nullptr, 0, 0, (const T*)j.gy, j.gy_ld,
+                                                 j.gy_off, j.scale, j.shift, j.mean_invstd, j.act, j.ws, ppb, fin));
+  }
+  return launch_status();
+}
+
+struct BiasPass {                            // dbias = sum over pixels of gy: reads gy, ws, counter, dbias of the job
+  using Job = yms_bn_pass_job;
+  using Dev = BiasJob;
+  static yms_status check(const Job& j) { return reduce_check(j, false, true); }
+  static bool groupable(const Job&) { return true; }
+  static unsigned blocks(const Job& j) { return pix_blocks(j.npix, fused_ppb(j)); }
+  static BwdFin fin(const Job& j) { return BwdFin{j.counter, nullptr, j.dbias, nullptr, j.npix}; }
+  static Dev dev(const Job& j) { return BiasJob{j.npix, fused_ppb(j), j.c, j.gy, j.gy_ld, j.gy_off, j.ws, fin(j)}; }
+  static yms_status launch_solo(int dtype, const Job& j, hipStream_t st) {
+    // (without z the kernel reads none of the job's z, scale, shift, mean_invstd, act: null / 0 in a bias job)
+    return launch_reduce_finalize(dtype, j, false, fin(j), st);
+  }
+  static yms_status launch_group(int dtype, const BnGroup<Dev>& g, unsigned nb, hipStream_t st) {
+    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(bias_bwd_group_kernel<T>, dim3(nb), dim3(256), 0, st, g));
+    return YMS_OK;
+  }
+};
+
+extern "C" {
+
+yms_status yms_bn_finalize_ld(int c, float* stats, int rows, int stats_ld, long count,
+                              const float* gamma, const float* beta, float* rmean, float* rvar,
+                              float momentum, float eps, float* mean_invstd, int mi_ld, float* scale,
+                              float* shift, void* stream) {
+  const yms_bn_finalize_job j{c, stats, rows, stats_ld, count, gamma, beta, rmean, rvar, momentum, eps,
+                              mean_invstd, mi_ld, scale, shift};
+  return run_pass<FinalizePass>(0, 1, &j, stream);
+}
+
+yms_status yms_bn_finalize(int c, float* stats, int rows, int stats_ld, long count,
+                           const float* gamma, const float* beta, float* rmean, float* rvar,
+                           float momentum, float eps, float* mean_invstd, float* scale,
+                           float* shift, void* stream) {
+  return yms_bn_finalize_ld(c, stats, rows, stats_ld, count, gamma, beta, rmean, rvar, momentum, eps,
+                            mean_invstd, c, scale, shift, stream);
+}
+
+yms_status yms_affine_act(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
+                          const float* scale, const float* shift, int act,
+                          const void* res, int res_ld, int res_off,
+                          void* y, int y_ld, int y_off, void* stream) {
+  const yms_bn_pass_job j{npix, c, z, z_ld, z_off, nullptr, 0, 0, scale, shift, nullptr, nullptr, act, y, y_ld, y_off,
+                          (void*)res, res_ld, res_off};
+  return run_pass<AffinePass>(dtype, 1, &j, stream);
+}
+
 // the number of partial rows the reduce WRITES = its launched block count ceil(npix / ppb).
 // Once a cap applies this can be below the cap (npix = 44801, c = 64: ppb 176, 255 blocks), so the
 // scratch size, the launch and the finalize all use this one function.
 int yms_bn_bwd_rows(long npix, int c) {
   if (npix <= 0 || c <= 0) return 0;
-  const long ppb = bwd_pix_per_block(npix, c, false);   // >= the fused path's rows: sizes both
-  return (int)((npix + ppb - 1) / ppb);
+  return (int)pix_blocks(npix, bwd_pix_per_block(npix, c, false));   // >= the fused path's rows: sizes both
 }
 
 yms_status yms_bn_act_bwd_reduce(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
                                  const void* gy, int gy_ld, int gy_off, const float* scale,
                                  const float* shift, const float* mean_invstd, int act,
                                  float* ws, void* stream) {
-  if (npix <= 0 || !gy || !ws || !vok(gy_ld, gy_off, c)) return YMS_ERR_INVALID;
-  if (z && (!vok(z_ld, z_off, c) || !scale || !shift || !mean_invstd)) return YMS_ERR_INVALID;
-  if (c > 2048) return YMS_ERR_UNSUPPORTED;
-  const long ppb = bwd_pix_per_block(npix, c, false);
-  const unsigned rows = (unsigned)((npix + ppb - 1) / ppb);
-  // software-pipelined loop (c % 8 == 0).  At 512 rows it was step-neutral over the serial loop
-  // (the reduce -10%, the apply after it +5%, profiles/r03zb_bn_reduce_pipe_ab.txt); with the
-  // latency hidden inside each block, half the blocks (256 rows, bwd_pix_per_block) win: YOLOv8-s
-  // 18.63 -> 18.32 ms/step, YOLO-MS-S 37.42 -> 37.28 ms (means of four interleaved runs each,
-  // profiles/r03zd_*, r03ze_*); serial at 256 rows is slower.
-#define YMS_RED(HZ)                                                                                      \
-  YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, HZ, false, true>), dim3(rows), dim3(256), 0, \
-                                               (hipStream_t)stream, npix, c, HZ ? (const T*)z : (const T*)nullptr, \
-                                               HZ ? z_ld : 0, HZ ? z_off : 0, (const T*)gy, gy_ld, gy_off, scale,  \
-                                               shift, mean_invstd, act, ws, ppb))
-  if (z) YMS_RED(true);
-  else YMS_RED(false);
-#undef YMS_RED
-  return launch_status();
+  const yms_bn_pass_job j{npix, c, z, z_ld, z_off, gy, gy_ld, gy_off, scale, shift, mean_invstd, nullptr, act,
+                          nullptr, 0, 0, nullptr, 0, 0, 0, ws};
+  return run_pass<ReducePass>(dtype, 1, &j, stream);
 }
 
 yms_status yms_bn_act_bwd_finalize(int c, const float* ws, int rows, long count, float* dgamma,
                                    float* dbeta, float* coef, void* stream) {
-  if (c <= 0 || !ws || rows <= 0 || count <= 0) return YMS_ERR_INVALID;
-  // (tried and dropped: float4 channel quads x 32 row lanes with every load of a lane in flight --
-  // 19.42 -> 19.65 ms; a latency-shaped 8-channel x 32-lane variant with 4x the blocks -- +0.15-0.3
-  // ms, profiles/r03q_bn_finalize_ab.txt: inside the step the finalize waits for CU slots, not loads)
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel<8>, dim3(cdiv(c, 32)), dim3(256), 0, (hipStream_t)stream, c, ws,
-                     rows, count, dgamma, dbeta, coef);
-  return launch_status();
+  const yms_bn_bwd_finalize_job j{c, ws, rows, count, dgamma, dbeta, coef};
+  return run_pass<BwdFinalizePass>(0, 1, &j, stream);
 }
 
 yms_status yms_bn_act_bwd_apply(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
@@ -1217,20 +1425,9 @@ yms_status yms_bn_act_bwd_apply(int dtype, long npix, int c, const void* z, int 
                                 const float* shift, const float* mean_invstd, const float* coef,
                                 int act, void* dz, int dz_ld, int dz_off,
                                 void* gres, int gres_ld, int gres_off, int gres_acc, void* stream) {
-  if (npix <= 0 || !z || !gy || !dz || !scale || !shift || !mean_invstd || !coef) return YMS_ERR_INVALID;
-  if (!vok(z_ld, z_off, c) || !vok(gy_ld, gy_off, c) || !vok(dz_ld, dz_off, c)) return YMS_ERR_INVALID;
-  if (gres && !vok(gres_ld, gres_off, c)) return YMS_ERR_INVALID;
-  if (c > 2048) return YMS_ERR_UNSUPPORTED;
-  // software-pipelined loop at eight U-pixel iterations per thread (half the blocks of the serial
-  // loop's best, four): YOLO-MS-S 37.27 -> 37.11 ms/step, YOLOv8-s 18.53 -> 18.49 ms (means of
-  // two interleaved runs; 4 / 16 iterations pipelined are slower, profiles/r03zf_bn_apply_pipe_ab.txt)
-  const long ppb = elem_ppb(npix, c, 8 * BN_U / BN_UA);    // the same pixels per block at any U
-  const unsigned blocks = (unsigned)((npix + ppb - 1) / ppb);
-  YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(blocks), dim3(256), 0,
-                                               (hipStream_t)stream, npix, c, (const T*)z, z_ld, z_off,
-                                               (const T*)gy, gy_ld, gy_off, scale, shift, mean_invstd, coef,
-                                               act, (T*)dz, dz_ld, dz_off, (T*)gres, gres_ld, gres_off, gres_acc, ppb));
-  return launch_status();
+  const yms_bn_pass_job j{npix, c, z, z_ld, z_off, gy, gy_ld, gy_off, scale, shift, mean_invstd, coef, act,
+                          dz, dz_ld, dz_off, gres, gres_ld, gres_off, gres_acc};
+  return run_pass<ApplyPass>(dtype, 1, &j, stream);
 }
 
 yms_status yms_bn_act_bwd_reduce_finalize(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
@@ -1238,241 +1435,36 @@ yms_status yms_bn_act_bwd_reduce_finalize(int dtype, long npix, int c, const voi
                                           const float* shift, const float* mean_invstd, int act, float* ws,
                                           unsigned* counter, float* dgamma, float* dbeta, float* coef,
                                           void* stream) {
-  if (npix <= 0 || !gy || !ws || !counter || !vok(gy_ld, gy_off, c)) return YMS_ERR_INVALID;
-  if (z && (!vok(z_ld, z_off, c) || !scale || !shift || !mean_invstd)) return YMS_ERR_INVALID;
-  if (c > 2048) return YMS_ERR_UNSUPPORTED;
-  const long ppb = bwd_pix_per_block(npix, c, true);
-  const unsigned rows = (unsigned)((npix + ppb - 1) / ppb);
-  const BwdFin fin{counter, dgamma, dbeta, coef, npix};
-  if (z) {
-    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, true>), dim3(rows), dim3(256), 0,
-                                                 (hipStream_t)stream, npix, c, (const T*)z, z_ld, z_off,
-                                                 (const T*)gy, gy_ld, gy_off, scale, shift, mean_invstd,
-                                                 act, ws, ppb, fin));
-  } else {
-    YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, true>), dim3(rows), dim3(256), 0,
-                                                 (hipStream_t)stream, npix, c, (const T*)nullptr, 0, 0,
-                                                 (const T*)gy, gy_ld, gy_off, scale, shift, mean_invstd,
-                                                 act, ws, ppb, fin));
-  }
-  return launch_status();
+  const yms_bn_pass_job j{npix, c, z, z_ld, z_off, gy, gy_ld, gy_off, scale, shift, mean_invstd, nullptr, act,
+                          nullptr, 0, 0, nullptr, 0, 0, 0, ws, counter};
+  if (yms_status e = reduce_check(j, z != nullptr, true)) return e;
+  return launch_reduce_finalize(dtype, j, z != nullptr, BwdFin{counter, dgamma, dbeta, coef, npix}, (hipStream_t)stream);
 }
 
 yms_status yms_bias_bwd(int dtype, long npix, int c, const void* gy, int gy_ld, int gy_off,
                         float* ws, unsigned* counter, float* dbias, void* stream) {
-  return yms_bn_act_bwd_reduce_finalize(dtype, npix, c, nullptr, 0, 0, gy, gy_ld, gy_off, nullptr, nullptr,
-                                        nullptr, YMS_ACT_NONE, ws, counter, nullptr, dbias, nullptr, stream);
+  const yms_bn_pass_job j{npix, c, nullptr, 0, 0, gy, gy_ld, gy_off, nullptr, nullptr, nullptr, nullptr, YMS_ACT_NONE,
+                          nullptr, 0, 0, nullptr, 0, 0, 0, ws, counter, dbias};
+  return run_pass<BiasPass>(dtype, 1, &j, stream);
 }
-
-}  // extern "C"
-
-// ---- grouped forms: the jobs the grouped kernel serves go out BN_GROUP_MAX per launch, each member
-// with its solo launch's block count and per-block ranges; a job alone, or one the grouped kernel does
-// not serve, takes the solo call (solo(i)), in job order after the grouped launches
-template <typename Job, typename Launch, typename Solo>
-static yms_status launch_bn_groups(int njobs, const std::vector<int>& idx, const std::vector<Job>& jobs,
-                                   const std::vector<unsigned>& blocks, Launch launch, Solo solo) {
-  std::vector<char> grouped(njobs, 0);
-  if (idx.size() >= 2) {
-    for (size_t i = 0; i < idx.size(); i += BN_GROUP_MAX) {
-      const int n = (int)std::min<size_t>(BN_GROUP_MAX, idx.size() - i);
-      if (n < 2) break;                      // a lone remainder: solo
-      BnGroup<Job> g{};
-      g.n = n;
-      for (int k = 0; k < n; ++k) {
-        g.job[k] = jobs[i + k];
-        g.first[k + 1] = g.first[k] + blocks[i + k];
-        grouped[idx[i + k]] = 1;
-      }
-      if (yms_status e = launch(g, g.first[n])) return e;
-      if (yms_status e = launch_status()) return e;
-    }
-  }
-  for (int i = 0; i < njobs; ++i)
-    if (!grouped[i])
-      if (yms_status e = solo(i)) return e;
-  return YMS_OK;
-}
-
-extern "C" {
 
 yms_status yms_bn_finalize_group(int njobs, const yms_bn_finalize_job* jobs, void* stream) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<FinJob> js;
-  std::vector<unsigned> blocks;
-  std::vector<int> idx;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_bn_finalize_job& j = jobs[i];
-    if (j.c <= 0 || !j.stats || j.rows <= 0 || j.count <= 0 || !j.gamma || !j.beta || !j.mean_invstd || !j.scale ||
-        !j.shift || j.stats_ld < j.c || j.mi_ld < j.c)
-      return YMS_ERR_INVALID;
-    if (j.rows > 1024) continue;             // long tables: the solo call's pre-reduction + wide finalize
-    js.push_back(FinJob{j.c, j.rows, j.stats_ld, j.mi_ld, j.stats, j.count, j.gamma, j.beta, j.rmean, j.rvar,
-                        j.momentum, j.eps, j.mean_invstd, j.scale, j.shift});
-    blocks.push_back((unsigned)cdiv(j.c, 8));
-    idx.push_back(i);
-  }
-  return launch_bn_groups(
-      njobs, idx, js, blocks,
-      [&](const BnGroup<FinJob>& g, unsigned nb) -> yms_status {
-        hipLaunchKernelGGL(bn_finalize_small_group_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, g);
-        return YMS_OK;
-      },
-      [&](int i) {
-        const yms_bn_finalize_job& j = jobs[i];
-        return yms_bn_finalize_ld(j.c, j.stats, j.rows, j.stats_ld, j.count, j.gamma, j.beta, j.rmean, j.rvar,
-                                  j.momentum, j.eps, j.mean_invstd, j.mi_ld, j.scale, j.shift, stream);
-      });
+  return run_pass<FinalizePass>(0, njobs, jobs, stream);
 }
-
-static PassJob pass_job(const yms_bn_pass_job& j, long ppb) {
-  return PassJob{j.npix, ppb, j.c, j.act, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale, j.shift,
-                 j.mean_invstd, j.coef, j.out, j.out_ld, j.out_off, j.res, j.res_ld, j.res_off, j.res_acc, j.ws};
-}
-
 yms_status yms_affine_act_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<PassJob> js;
-  std::vector<unsigned> blocks;
-  std::vector<int> idx;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_bn_pass_job& j = jobs[i];
-    if (j.npix <= 0 || !j.z || !j.out || !vok(j.z_ld, j.z_off, j.c) || !vok(j.out_ld, j.out_off, j.c))
-      return YMS_ERR_INVALID;
-    if (j.res && !vok(j.res_ld, j.res_off, j.c)) return YMS_ERR_INVALID;
-    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
-    const long ppb = elem_ppb(j.npix, j.c, 2);            // as yms_affine_act
-    js.push_back(pass_job(j, ppb));
-    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
-    idx.push_back(i);
-  }
-  return launch_bn_groups(
-      njobs, idx, js, blocks,
-      [&](const BnGroup<PassJob>& g, unsigned nb) -> yms_status {
-        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((affine_act_group_kernel<T, true>), dim3(nb), dim3(256), 0,
-                                                     (hipStream_t)stream, g));
-        return YMS_OK;
-      },
-      [&](int i) {
-        const yms_bn_pass_job& j = jobs[i];
-        return yms_affine_act(dtype, j.npix, j.c, j.z, j.z_ld, j.z_off, j.scale, j.shift, j.act, j.res, j.res_ld,
-                              j.res_off, j.out, j.out_ld, j.out_off, stream);
-      });
+  return run_pass<AffinePass>(dtype, njobs, jobs, stream);
 }
-
 yms_status yms_bn_act_bwd_reduce_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<PassJob> js;
-  std::vector<unsigned> blocks;
-  std::vector<int> idx;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_bn_pass_job& j = jobs[i];
-    if (j.npix <= 0 || !j.gy || !j.ws || !vok(j.gy_ld, j.gy_off, j.c)) return YMS_ERR_INVALID;
-    if (j.z && (!vok(j.z_ld, j.z_off, j.c) || !j.scale || !j.shift || !j.mean_invstd)) return YMS_ERR_INVALID;
-    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
-    if (!j.z) continue;                                    // the plain column sum: solo
-    const long ppb = bwd_pix_per_block(j.npix, j.c, false);
-    js.push_back(pass_job(j, ppb));
-    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
-    idx.push_back(i);
-  }
-  return launch_bn_groups(
-      njobs, idx, js, blocks,
-      [&](const BnGroup<PassJob>& g, unsigned nb) -> yms_status {
-        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(bn_bwd_reduce_group_kernel<T>, dim3(nb), dim3(256), 0,
-                                                     (hipStream_t)stream, g));
-        return YMS_OK;
-      },
-      [&](int i) {
-        const yms_bn_pass_job& j = jobs[i];
-        return yms_bn_act_bwd_reduce(dtype, j.npix, j.c, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale,
-                                     j.shift, j.mean_invstd, j.act, j.ws, stream);
-      });
+  return run_pass<ReducePass>(dtype, njobs, jobs, stream);
 }
-
 yms_status yms_bn_act_bwd_finalize_group(int njobs, const yms_bn_bwd_finalize_job* jobs, void* stream) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<BwdFinJob> js;
-  std::vector<unsigned> blocks;
-  std::vector<int> idx;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_bn_bwd_finalize_job& j = jobs[i];
-    if (j.c <= 0 || !j.ws || j.rows <= 0 || j.count <= 0) return YMS_ERR_INVALID;
-    js.push_back(BwdFinJob{j.c, j.rows, j.ws, j.count, j.dgamma, j.dbeta, j.coef});
-    blocks.push_back((unsigned)cdiv(j.c, 32));
-    idx.push_back(i);
-  }
-  return launch_bn_groups(
-      njobs, idx, js, blocks,
-      [&](const BnGroup<BwdFinJob>& g, unsigned nb) -> yms_status {
-        hipLaunchKernelGGL(bn_bwd_finalize_group_kernel<8>, dim3(nb), dim3(256), 0, (hipStream_t)stream, g);
-        return YMS_OK;
-      },
-      [&](int i) {
-        const yms_bn_bwd_finalize_job& j = jobs[i];
-        return yms_bn_act_bwd_finalize(j.c, j.ws, j.rows, j.count, j.dgamma, j.dbeta, j.coef, stream);
-      });
+  return run_pass<BwdFinalizePass>(0, njobs, jobs, stream);
 }
-
 yms_status yms_bn_act_bwd_apply_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<PassJob> js;
-  std::vector<unsigned> blocks;
-  std::vector<int> idx;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_bn_pass_job& j = jobs[i];
-    if (j.npix <= 0 || !j.z || !j.gy || !j.out || !j.scale || !j.shift || !j.mean_invstd || !j.coef)
-      return YMS_ERR_INVALID;
-    if (!vok(j.z_ld, j.z_off, j.c) || !vok(j.gy_ld, j.gy_off, j.c) || !vok(j.out_ld, j.out_off, j.c))
-      return YMS_ERR_INVALID;
-    if (j.res && !vok(j.res_ld, j.res_off, j.c)) return YMS_ERR_INVALID;
-    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
-    const long ppb = elem_ppb(j.npix, j.c, 8 * BN_U / BN_UA);   // as yms_bn_act_bwd_apply
-    js.push_back(pass_job(j, ppb));
-    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
-    idx.push_back(i);
-  }
-  return launch_bn_groups(
-      njobs, idx, js, blocks,
-      [&](const BnGroup<PassJob>& g, unsigned nb) -> yms_status {
-        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_bwd_apply_group_kernel<T, true>), dim3(nb), dim3(256), 0,
-                                                     (hipStream_t)stream, g));
-        return YMS_OK;
-      },
-      [&](int i) {
-        const yms_bn_pass_job& j = jobs[i];
-        return yms_bn_act_bwd_apply(dtype, j.npix, j.c, j.z, j.z_ld, j.z_off, j.gy, j.gy_ld, j.gy_off, j.scale,
-                                    j.shift, j.mean_invstd, j.coef, j.act, j.out, j.out_ld, j.out_off, j.res,
-                                    j.res_ld, j.res_off, j.res_acc, stream);
-      });
+  return run_pass<ApplyPass>(dtype, njobs, jobs, stream);
 }
-
 yms_status yms_bias_bwd_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<BiasJob> js;
-  std::vector<unsigned> blocks;
-  std::vector<int> idx;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_bn_pass_job& j = jobs[i];
-    if (j.npix <= 0 || !j.gy || !j.ws || !j.counter || !vok(j.gy_ld, j.gy_off, j.c)) return YMS_ERR_INVALID;
-    if (j.c > 2048) return YMS_ERR_UNSUPPORTED;
-    const long ppb = bwd_pix_per_block(j.npix, j.c, true);       // as yms_bn_act_bwd_reduce_finalize
-    js.push_back(BiasJob{j.npix, ppb, j.c, j.gy, j.gy_ld, j.gy_off, j.ws,
-                         BwdFin{j.counter, nullptr, j.dbias, nullptr, j.npix}});
-    blocks.push_back((unsigned)((j.npix + ppb - 1) / ppb));
-    idx.push_back(i);
-  }
-  return launch_bn_groups(
-      njobs, idx, js, blocks,
-      [&](const BnGroup<BiasJob>& g, unsigned nb) -> yms_status {
-        YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(bias_bwd_group_kernel<T>, dim3(nb), dim3(256), 0,
-                                                     (hipStream_t)stream, g));
-        return YMS_OK;
-      },
-      [&](int i) {
-        const yms_bn_pass_job& j = jobs[i];
-        return yms_bias_bwd(dtype, j.npix, j.c, j.gy, j.gy_ld, j.gy_off, j.ws, j.counter, j.dbias, stream);
-      });
+  return run_pass<BiasPass>(dtype, njobs, jobs, stream);
 }
 
 size_t yms_sppf_ws_bytes(int n, int h, int w, int c) {

@@ -1258,6 +1258,37 @@ static TileChoice choose_tile(int ncols) {
   return TileChoice{0, 128};
 }
 
+// The ONE route decision of a forward (dgrad = 0) or input gradient (dgrad = 1) with epilogue epi: the
+// solo entry points, launch_nt and the grouped calls all read it.
+struct ConvRoute {
+  enum Kind {
+    DIRECT,              // small-channel 3x3: conv_direct_kernel (conv_direct.hip), geometry dg
+    NT,                  // conv_nt_kernel: fp32, and 16-bit affine outputs wider than NTP_MAX_AFFINE_COLS
+    NTP                  // persistent 16-bit conv_ntp_kernel, with the UNI loader when uni
+  } kind;
+  bool parity;           // stride-2 input gradient: the four output parity classes (MODE_DGRAD2)
+  int cfg;               // tile config of NT / NTP (choose_tile)
+  bool uni;
+  DirectGeo dg;
+  PackGeo pg;            // the GEMM's K geometry (conv_params reads it), or the parity classes' d2
+  Dg2Geo d2;
+  // the grouped kernel serves the persistent stride-1 GEMM in its two wide tile configs (the 32-column
+  // one no grouped caller has needed)
+  bool groupable() const { return kind == NTP && !parity && (cfg == 0 || cfg == 1); }
+};
+static ConvRoute conv_route(const yms_conv_shape* s, int dgrad, int epi) {
+  ConvRoute r{};
+  if (conv_direct_geometry(s, dgrad, &r.dg)) return r;
+  const int ncols = dgrad ? s->cin : s->cout;
+  r.parity = dgrad && s->stride == 2;
+  r.cfg = choose_tile(ncols).cfg;
+  r.kind = s->dtype == YMS_F32 || (epi == EPI_AFFINE && ncols > NTP_MAX_AFFINE_COLS) ? ConvRoute::NT : ConvRoute::NTP;
+  if (r.parity) r.d2 = dg2_geo(s);
+  else r.pg = pack_geo(s, dgrad);
+  r.uni = (r.parity ? r.d2.cpt : r.pg.cpt) % NT_KCH == 0;
+  return r;
+}
+
 static int cu_count() { return conv_cu_count(); }
 
 // forward: statistics (training) grids persistent at 1x (the side-stream wgrads hold CUs: 4x
@@ -1317,12 +1348,13 @@ static void launch_ntp(const NTParams& p0, int cfg, unsigned gy, hipStream_t st)
 }
 
 template <typename T, int KS, int MODE, int EPI>
-static void launch_nt(const NTParams& p0, int cfg, hipStream_t st) {
+static void launch_nt(const NTParams& p0, const ConvRoute& r, hipStream_t st) {
   NTParams p = p0;
+  const int cfg = r.cfg;
   const unsigned gy = MODE == MODE_DGRAD2 ? 4u : 1u;
   if constexpr (sizeof(T) == 2) {
-    if (EPI != EPI_AFFINE || p.Ncols <= NTP_MAX_AFFINE_COLS) {
-      if (p.cpt % NT_KCH == 0) launch_ntp<T, KS, MODE, EPI, true>(p, cfg, gy, st);
+    if (r.kind == ConvRoute::NTP) {
+      if (r.uni) launch_ntp<T, KS, MODE, EPI, true>(p, cfg, gy, st);
       else launch_ntp<T, KS, MODE, EPI, false>(p, cfg, gy, st);
       return;
     }
@@ -1357,11 +1389,11 @@ static bool set_src_geometry(NTParams& p, long n, long h, long w, long ld, int e
 static bool offsets32(long n, long h, long w, long ld) { return n * h * w * ld < (1l << 31) - (1l << 20); }
 
 template <int MODE, int EPI>
-static yms_status dispatch_nt(const NTParams& p, int dtype, int ks, int cfg, hipStream_t st) {
+static yms_status dispatch_nt(const NTParams& p, int dtype, int ks, const ConvRoute& r, hipStream_t st) {
 #define YMS_NT_CASE(T)                                          \
-  if constexpr (MODE == MODE_DGRAD2) launch_nt<T, 3, MODE, EPI>(p, cfg, st);   \
-  else if (ks == 1) launch_nt<T, 1, MODE, EPI>(p, cfg, st);     \
-  else launch_nt<T, 3, MODE, EPI>(p, cfg, st);
+  if constexpr (MODE == MODE_DGRAD2) launch_nt<T, 3, MODE, EPI>(p, r, st);   \
+  else if (ks == 1) launch_nt<T, 1, MODE, EPI>(p, r, st);     \
+  else launch_nt<T, 3, MODE, EPI>(p, r, st);
   if (dtype == YMS_BF16) { YMS_NT_CASE(bf16) }
   else if (dtype == YMS_F16) { YMS_NT_CASE(f16) }
   else { YMS_NT_CASE(float) }
@@ -1549,27 +1581,26 @@ int yms_conv_stats_ld(const yms_conv_shape* s) {
 }  // extern "C"
 
 // The implicit-GEMM forward's kernel parameters (everything but tiles_n, which the launch sets from
-// its tile shape): shared by yms_conv_fwd and yms_conv_fwd_group.
-static yms_status fwd_params(const yms_conv_shape* s, const void* x, int x_ld, int x_off, const void* wpacked,
-                             void* y, int y_ld, int y_off, const float* scale, const float* shift, int act,
-                             const void* res, int res_ld, int res_off, float* stats, NTParams& p) {
+// its tile shape): shared by the solo and the grouped forward.
+static yms_status conv_params(const yms_conv_fwd_job& j, const ConvRoute& r, NTParams& p) {
+  const yms_conv_shape* s = &j.shape;
   const int es = elem_size(s->dtype);
-  PackGeo g = pack_geo(s, 0);
+  const PackGeo& g = r.pg;
   p = NTParams{};
-  p.src = (const char*)x;
-  p.wp = (const char*)wpacked;
-  p.dst = (char*)y;
-  p.src_ld = x_ld; p.src_off = x_off; p.dst_ld = y_ld; p.dst_off = y_off;
-  p.scale = scale; p.shift = shift; p.act = act;
-  p.res = (const char*)res; p.res_ld = res_ld; p.res_off = res_off;
-  p.stats = stats;
+  p.src = (const char*)j.x;
+  p.wp = (const char*)j.wpacked;
+  p.dst = (char*)j.y;
+  p.src_ld = j.x_ld; p.src_off = j.x_off; p.dst_ld = j.y_ld; p.dst_off = j.y_off;
+  p.scale = j.scale; p.shift = j.shift; p.act = j.act;
+  p.res = (const char*)j.res; p.res_ld = j.res_ld; p.res_off = j.res_off;
+  p.stats = j.stats;
   p.stats_ld = (int)rup(s->cout, 128);
-  if (stats) p.stats_cnt = stats + (long)yms_conv_stats_rows(s) * 2 * p.stats_ld;
+  if (j.stats) p.stats_cnt = j.stats + (long)yms_conv_stats_rows(s) * 2 * p.stats_ld;
   p.SH = s->h; p.SW = s->w; p.OW = s->wo;
-  if (!offsets32(s->n, s->h, s->w, x_ld)) return YMS_ERR_UNSUPPORTED;
+  if (!offsets32(s->n, s->h, s->w, j.x_ld)) return YMS_ERR_UNSUPPORTED;
   p.stride = s->stride; p.pad = s->pad;
   p.cpt = g.cpt; p.Kc = g.kc; p.nkt = g.nkt;
-  if (!set_src_geometry(p, s->n, s->h, s->w, x_ld, es, g.nkt * NT_KCH)) return YMS_ERR_UNSUPPORTED;
+  if (!set_src_geometry(p, s->n, s->h, s->w, j.x_ld, es, g.nkt * NT_KCH)) return YMS_ERR_UNSUPPORTED;
   p.M = s->n * s->ho * s->wo;
   p.Ncols = s->cout;
   p.div_ow = make_fastdiv(s->wo);
@@ -1577,78 +1608,104 @@ static yms_status fwd_params(const yms_conv_shape* s, const void* x, int x_ld, i
   return YMS_OK;
 }
 
-static bool fwd_args_ok(const yms_conv_shape* s, const void* x, int x_ld, int x_off, const void* wpacked,
-                        const void* y, int y_ld, int y_off, const void* res, int res_ld, int res_off) {
-  if (!shape_ok(s) || !x || !wpacked || !y) return false;
-  if (!view_ok(x_ld, x_off, s->cin) || !view_ok(y_ld, y_off, s->cout)) return false;
-  return !res || view_ok(res_ld, res_off, s->cout);
+static bool args_ok(const yms_conv_fwd_job& j) {
+  const yms_conv_shape* s = &j.shape;
+  if (!shape_ok(s) || !j.x || !j.wpacked || !j.y) return false;
+  if (!view_ok(j.x_ld, j.x_off, s->cin) || !view_ok(j.y_ld, j.y_off, s->cout)) return false;
+  return !j.res || view_ok(j.res_ld, j.res_off, s->cout);
 }
+static int epi_of(const yms_conv_fwd_job& j) { return j.stats ? EPI_STATS : EPI_AFFINE; }
+static ConvRoute route_of(const yms_conv_fwd_job& j) { return conv_route(&j.shape, 0, epi_of(j)); }
 
-extern "C" {
-
-yms_status yms_conv_fwd(const yms_conv_shape* s, const void* x, int x_ld, int x_off,
-                        const void* wpacked, void* y, int y_ld, int y_off,
-                        const float* scale, const float* shift, int act,
-                        const void* res, int res_ld, int res_off, float* stats, void* stream) {
-  if (!fwd_args_ok(s, x, x_ld, x_off, wpacked, y, y_ld, y_off, res, res_ld, res_off)) return YMS_ERR_INVALID;
-  {
-    // small-channel 3x3: the direct kernel (conv_direct.hip), statistics included
-    DirectGeo dg;
-    if (conv_direct_geometry(s, 0, &dg))
-      return conv_direct_launch(s, 0, dg, x, x_ld, x_off, wpacked, y, y_ld, y_off, scale, shift, act, res, res_ld,
-                                res_off, stats, 0, (hipStream_t)stream);
-  }
+// One forward (arguments checked), solo: yms_conv_fwd, and the grouped call's jobs that no group takes.
+static yms_status conv_solo(const yms_conv_fwd_job& j, const ConvRoute& r, hipStream_t st) {
+  const yms_conv_shape* s = &j.shape;
+  if (r.kind == ConvRoute::DIRECT)          // statistics included
+    return conv_direct_launch(s, 0, r.dg, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.scale, j.shift,
+                              j.act, j.res, j.res_ld, j.res_off, j.stats, 0, st);
   NTParams p;
-  if (yms_status e = fwd_params(s, x, x_ld, x_off, wpacked, y, y_ld, y_off, scale, shift, act, res, res_ld, res_off,
-                                stats, p))
-    return e;
-  TileChoice tc = choose_tile(s->cout);
-  hipStream_t st = (hipStream_t)stream;
-  if (stats) return dispatch_nt<MODE_FWD, EPI_STATS>(p, s->dtype, s->k, tc.cfg, st);
-  return dispatch_nt<MODE_FWD, EPI_AFFINE>(p, s->dtype, s->k, tc.cfg, st);
+  if (yms_status e = conv_params(j, r, p)) return e;
+  if (j.stats) return dispatch_nt<MODE_FWD, EPI_STATS>(p, s->dtype, s->k, r, st);
+  return dispatch_nt<MODE_FWD, EPI_AFFINE>(p, s->dtype, s->k, r, st);
 }
 
-}  // extern "C"
-
-static bool dgrad_args_ok(const yms_conv_shape* s, const void* dz, int dz_ld, int dz_off, const void* wpacked_t,
-                          const void* dx, int dx_ld, int dx_off) {
-  if (!shape_ok(s) || !dz || !wpacked_t || !dx) return false;
-  return view_ok(dz_ld, dz_off, s->cout) && view_ok(dx_ld, dx_off, s->cin);
+static bool args_ok(const yms_conv_dgrad_job& j) {
+  const yms_conv_shape* s = &j.shape;
+  if (!shape_ok(s) || !j.dz || !j.wpacked_t || !j.dx) return false;
+  return view_ok(j.dz_ld, j.dz_off, s->cout) && view_ok(j.dx_ld, j.dx_off, s->cin);
 }
+static int epi_of(const yms_conv_dgrad_job& j) { return j.accumulate ? EPI_ACCUM : EPI_STORE; }
+static ConvRoute route_of(const yms_conv_dgrad_job& j) { return conv_route(&j.shape, 1, epi_of(j)); }
 
-// the input gradient's kernel parameters common to both strides ...
-static void dgrad_params(const yms_conv_shape* s, const void* dz, int dz_ld, int dz_off, const void* wpacked_t,
-                         void* dx, int dx_ld, int dx_off, NTParams& p) {
+// The input gradient's kernel parameters: those common to both strides, then the stride-1 GEMM's or the
+// parity classes' geometry (YMS_ERR_UNSUPPORTED: extent).  p.M == 0: nothing to launch.
+static yms_status conv_params(const yms_conv_dgrad_job& j, const ConvRoute& r, NTParams& p) {
+  const yms_conv_shape* s = &j.shape;
+  const int es = elem_size(s->dtype);
   p = NTParams{};
-  p.src = (const char*)dz;
-  p.wp = (const char*)wpacked_t;
-  p.dst = (char*)dx;
-  p.src_ld = dz_ld; p.src_off = dz_off; p.dst_ld = dx_ld; p.dst_off = dx_off;
+  p.src = (const char*)j.dz;
+  p.wp = (const char*)j.wpacked_t;
+  p.dst = (char*)j.dx;
+  p.src_ld = j.dz_ld; p.src_off = j.dz_off; p.dst_ld = j.dx_ld; p.dst_off = j.dx_off;
   p.SH = s->ho; p.SW = s->wo; p.OW = s->w;
   p.stride = s->stride; p.pad = s->pad;
   p.Ncols = s->cin;
   p.OH = s->h; p.OWx = s->w;
+  if (!offsets32(s->n, s->ho, s->wo, j.dz_ld)) return YMS_ERR_UNSUPPORTED;
+  if (!r.parity) {
+    const PackGeo& g = r.pg;
+    p.cpt = g.cpt; p.Kc = g.kc; p.nkt = g.nkt;
+    if (!set_src_geometry(p, s->n, s->ho, s->wo, j.dz_ld, es, g.nkt * NT_KCH)) return YMS_ERR_UNSUPPORTED;
+    p.M = s->n * s->h * s->w;
+    p.div_ow = make_fastdiv(s->w);
+    p.div_ohw = make_fastdiv(s->h * s->w);
+    return YMS_OK;
+  }
+  const Dg2Geo& d = r.d2;
+  p.cpt = d.cpt;
+  if (!set_src_geometry(p, s->n, s->ho, s->wo, j.dz_ld, es, *std::max_element(d.nkt, d.nkt + 4) * NT_KCH))
+    return YMS_ERR_UNSUPPORTED;
+  p.M = 0;
+  for (int c = 0; c < 4; ++c) {
+    p.cls_M[c] = d.M[c];
+    p.cls_nkt[c] = d.nkt[c];
+    p.cls_Kc[c] = d.Kc[c];
+    p.cls_ntx[c] = d.ntx[c];
+    p.cls_c0y[c] = d.c0y[c];
+    p.cls_c0x[c] = d.c0x[c];
+    p.cls_woff[c] = d.off_elems[c] * es;
+    p.cls_div_w[c] = make_fastdiv(std::max(1, d.Wa[c]));
+    p.cls_div_hw[c] = make_fastdiv(std::max(1, d.Ha[c] * d.Wa[c]));
+    p.M = std::max(p.M, d.M[c]);
+  }
+  return YMS_OK;
 }
 
-// ... and the stride-1 GEMM's geometry (false: unsupported extent)
-static bool dgrad1_geometry(const yms_conv_shape* s, int dz_ld, NTParams& p) {
-  PackGeo g = pack_geo(s, 1);
-  p.cpt = g.cpt; p.Kc = g.kc; p.nkt = g.nkt;
-  if (!set_src_geometry(p, s->n, s->ho, s->wo, dz_ld, elem_size(s->dtype), g.nkt * NT_KCH)) return false;
-  p.M = s->n * s->h * s->w;
-  p.div_ow = make_fastdiv(s->w);
-  p.div_ohw = make_fastdiv(s->h * s->w);
-  return true;
+// One input gradient (arguments checked), solo.
+static yms_status conv_solo(const yms_conv_dgrad_job& j, const ConvRoute& r, hipStream_t st) {
+  const yms_conv_shape* s = &j.shape;
+  if (r.kind == ConvRoute::DIRECT)
+    return conv_direct_launch(s, 1, r.dg, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off, nullptr,
+                              nullptr, 0, nullptr, 0, 0, nullptr, j.accumulate, st);
+  NTParams p;
+  if (yms_status e = conv_params(j, r, p)) return e;
+  if (r.parity) {
+    if (p.M == 0) return YMS_OK;
+    if (j.accumulate) return dispatch_nt<MODE_DGRAD2, EPI_ACCUM>(p, s->dtype, s->k, r, st);
+    return dispatch_nt<MODE_DGRAD2, EPI_STORE>(p, s->dtype, s->k, r, st);
+  }
+  if (j.accumulate) return dispatch_nt<MODE_DGRAD, EPI_ACCUM>(p, s->dtype, s->k, r, st);
+  return dispatch_nt<MODE_DGRAD, EPI_STORE>(p, s->dtype, s->k, r, st);
 }
 
 // One job of a grouped call: key < 0 runs through the solo entry point.
 struct GroupMember {
   int job, key = -1;
+  ConvRoute r;
   NTParams p;
 };
-static bool group_cfg_ok(int cfg) { return cfg == 0 || cfg == 1; }
-static int group_key(int dtype, int ks, int epi, int cfg, bool uni) {
-  return (((dtype * 4 + ks) * 8 + epi) * 4 + cfg) * 2 + (uni ? 1 : 0);
+static int group_key(const yms_conv_shape& s, int epi, const ConvRoute& r) {
+  return (((s.dtype * 4 + s.k) * 8 + epi) * 4 + r.cfg) * 2 + (r.uni ? 1 : 0);
 }
 
 // Mirrors launch_ntp for n members of one key: each member's tiles_n and grid as its solo launch.
@@ -1726,123 +1783,63 @@ static yms_status launch_groups(const std::vector<GroupMember>& ms, hipStream_t 
   return YMS_OK;
 }
 
+// ---- grouped launches -----------------------------------------------------------------------
+// The jobs of one call are partitioned by kernel template key (dtype, k, epilogue, tile config,
+// UNI loader); each key's members go out NT_GROUP_MAX at a time as one conv_ntp_group_kernel launch.
+// A job alone in its key, and every job whose route is not groupable (ConvRoute: the direct 3x3
+// route, fp32, the stride-2 input gradient, affine outputs wider than NTP_MAX_AFFINE_COLS, the
+// 32-column tile config), runs as its solo call, in job order.
+template <int MODE, typename Job>
+static yms_status conv_group(int njobs, const Job* jobs, void* stream, int* count) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
+  std::vector<GroupMember> ms;
+  for (int i = 0; i < njobs; ++i) {
+    if (!args_ok(jobs[i])) return YMS_ERR_INVALID;
+    GroupMember m{};
+    m.job = i;
+    m.r = route_of(jobs[i]);
+    if (m.r.groupable()) {
+      if (yms_status e = conv_params(jobs[i], m.r, m.p)) return e;
+      m.key = group_key(jobs[i].shape, epi_of(jobs[i]), m.r);
+    }
+    ms.push_back(m);
+  }
+  return launch_groups<MODE>(ms, (hipStream_t)stream,
+                             [&](int i) { return conv_solo(jobs[i], ms[i].r, (hipStream_t)stream); }, count);
+}
+
 extern "C" {
+
+yms_status yms_conv_fwd(const yms_conv_shape* s, const void* x, int x_ld, int x_off,
+                        const void* wpacked, void* y, int y_ld, int y_off,
+                        const float* scale, const float* shift, int act,
+                        const void* res, int res_ld, int res_off, float* stats, void* stream) {
+  if (!s) return YMS_ERR_INVALID;
+  const yms_conv_fwd_job j{*s, x, x_ld, x_off, wpacked, y, y_ld, y_off, scale, shift, act, res, res_ld, res_off, stats};
+  return args_ok(j) ? conv_solo(j, route_of(j), (hipStream_t)stream) : YMS_ERR_INVALID;
+}
 
 yms_status yms_conv_dgrad(const yms_conv_shape* s, const void* dz, int dz_ld, int dz_off,
                           const void* wpacked_t, void* dx, int dx_ld, int dx_off,
                           int accumulate, void* stream) {
-  if (!dgrad_args_ok(s, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off)) return YMS_ERR_INVALID;
-  {
-    DirectGeo dg;
-    if (conv_direct_geometry(s, 1, &dg))
-      return conv_direct_launch(s, 1, dg, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off, nullptr, nullptr, 0,
-                                nullptr, 0, 0, nullptr, accumulate, (hipStream_t)stream);
-  }
-  NTParams p;
-  dgrad_params(s, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off, p);
-  if (!offsets32(s->n, s->ho, s->wo, dz_ld)) return YMS_ERR_UNSUPPORTED;
-  TileChoice tc = choose_tile(s->cin);
-  hipStream_t st = (hipStream_t)stream;
-  if (s->stride == 2) {
-    Dg2Geo d = dg2_geo(s);
-    const int es = elem_size(s->dtype);
-    p.cpt = d.cpt;
-    if (!set_src_geometry(p, s->n, s->ho, s->wo, dz_ld, es, *std::max_element(d.nkt, d.nkt + 4) * NT_KCH))
-      return YMS_ERR_UNSUPPORTED;
-    p.M = 0;
-    for (int c = 0; c < 4; ++c) {
-      p.cls_M[c] = d.M[c];
-      p.cls_nkt[c] = d.nkt[c];
-      p.cls_Kc[c] = d.Kc[c];
-      p.cls_ntx[c] = d.ntx[c];
-      p.cls_c0y[c] = d.c0y[c];
-      p.cls_c0x[c] = d.c0x[c];
-      p.cls_woff[c] = d.off_elems[c] * es;
-      p.cls_div_w[c] = make_fastdiv(std::max(1, d.Wa[c]));
-      p.cls_div_hw[c] = make_fastdiv(std::max(1, d.Ha[c] * d.Wa[c]));
-      p.M = std::max(p.M, d.M[c]);
-    }
-    if (p.M == 0) return YMS_OK;
-    if (accumulate) return dispatch_nt<MODE_DGRAD2, EPI_ACCUM>(p, s->dtype, s->k, tc.cfg, st);
-    return dispatch_nt<MODE_DGRAD2, EPI_STORE>(p, s->dtype, s->k, tc.cfg, st);
-  }
-  if (!dgrad1_geometry(s, dz_ld, p)) return YMS_ERR_UNSUPPORTED;
-  if (accumulate) return dispatch_nt<MODE_DGRAD, EPI_ACCUM>(p, s->dtype, s->k, tc.cfg, st);
-  return dispatch_nt<MODE_DGRAD, EPI_STORE>(p, s->dtype, s->k, tc.cfg, st);
+  if (!s) return YMS_ERR_INVALID;
+  const yms_conv_dgrad_job j{*s, dz, dz_ld, dz_off, wpacked_t, dx, dx_ld, dx_off, accumulate};
+  return args_ok(j) ? conv_solo(j, route_of(j), (hipStream_t)stream) : YMS_ERR_INVALID;
 }
 
-// ---- grouped launches -----------------------------------------------------------------------
-// The jobs of one call are partitioned by kernel template key (dtype, k, epilogue, tile config,
-// UNI loader); each key's members go out NT_GROUP_MAX at a time as one conv_ntp_group_kernel launch.
-// A job alone in its key, and every job the persistent 16-bit kernel does not serve (the direct 3x3
-// route, fp32, the stride-2 input gradient, affine outputs wider than NTP_MAX_AFFINE_COLS, the
-// 32-column tile config, which no grouped caller has needed), runs through its solo entry point, in
-// job order.
-static yms_status fwd_group(int njobs, const yms_conv_fwd_job* jobs, void* stream, int* count) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<GroupMember> ms;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_conv_fwd_job& j = jobs[i];
-    const yms_conv_shape* s = &j.shape;
-    if (!fwd_args_ok(s, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.res, j.res_ld, j.res_off))
-      return YMS_ERR_INVALID;
-    GroupMember m{};
-    m.job = i;
-    DirectGeo dg;
-    const int cfg = choose_tile(s->cout).cfg;
-    const int epi = j.stats ? EPI_STATS : EPI_AFFINE;
-    if (s->dtype != YMS_F32 && !conv_direct_geometry(s, 0, &dg) && group_cfg_ok(cfg) &&
-        (epi != EPI_AFFINE || s->cout <= NTP_MAX_AFFINE_COLS)) {
-      if (yms_status e = fwd_params(s, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.scale, j.shift, j.act,
-                                    j.res, j.res_ld, j.res_off, j.stats, m.p))
-        return e;
-      m.key = group_key(s->dtype, s->k, epi, cfg, m.p.cpt % NT_KCH == 0);
-    }
-    ms.push_back(m);
-  }
-  return launch_groups<MODE_FWD>(ms, (hipStream_t)stream, [&](int i) {
-    const yms_conv_fwd_job& j = jobs[i];
-    return yms_conv_fwd(&j.shape, j.x, j.x_ld, j.x_off, j.wpacked, j.y, j.y_ld, j.y_off, j.scale, j.shift, j.act, j.res,
-                        j.res_ld, j.res_off, j.stats, stream);
-  }, count);
-}
 yms_status yms_conv_fwd_group(int njobs, const yms_conv_fwd_job* jobs, void* stream) {
-  return fwd_group(njobs, jobs, stream, nullptr);
+  return conv_group<MODE_FWD>(njobs, jobs, stream, nullptr);
 }
 int yms_conv_fwd_group_launches(int njobs, const yms_conv_fwd_job* jobs) {
   int n = 0;
-  return fwd_group(njobs, jobs, nullptr, &n) == YMS_OK ? n : -1;
-}
-
-static yms_status dgrad_group(int njobs, const yms_conv_dgrad_job* jobs, void* stream, int* count) {
-  if (njobs < 0 || (njobs > 0 && !jobs)) return YMS_ERR_INVALID;
-  std::vector<GroupMember> ms;
-  for (int i = 0; i < njobs; ++i) {
-    const yms_conv_dgrad_job& j = jobs[i];
-    const yms_conv_shape* s = &j.shape;
-    if (!dgrad_args_ok(s, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off)) return YMS_ERR_INVALID;
-    GroupMember m{};
-    m.job = i;
-    DirectGeo dg;
-    const int cfg = choose_tile(s->cin).cfg;
-    if (s->dtype != YMS_F32 && s->stride == 1 && !conv_direct_geometry(s, 1, &dg) && group_cfg_ok(cfg)) {
-      dgrad_params(s, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off, m.p);
-      if (!offsets32(s->n, s->ho, s->wo, j.dz_ld) || !dgrad1_geometry(s, j.dz_ld, m.p)) return YMS_ERR_UNSUPPORTED;
-      m.key = group_key(s->dtype, s->k, j.accumulate ? EPI_ACCUM : EPI_STORE, cfg, m.p.cpt % NT_KCH == 0);
-    }
-    ms.push_back(m);
-  }
-  return launch_groups<MODE_DGRAD>(ms, (hipStream_t)stream, [&](int i) {
-    const yms_conv_dgrad_job& j = jobs[i];
-    return yms_conv_dgrad(&j.shape, j.dz, j.dz_ld, j.dz_off, j.wpacked_t, j.dx, j.dx_ld, j.dx_off, j.accumulate, stream);
-  }, count);
+  return conv_group<MODE_FWD>(njobs, jobs, nullptr, &n) == YMS_OK ? n : -1;
 }
 yms_status yms_conv_dgrad_group(int njobs, const yms_conv_dgrad_job* jobs, void* stream) {
-  return dgrad_group(njobs, jobs, stream, nullptr);
+  return conv_group<MODE_DGRAD>(njobs, jobs, stream, nullptr);
 }
 int yms_conv_dgrad_group_launches(int njobs, const yms_conv_dgrad_job* jobs) {
   int n = 0;
-  return dgrad_group(njobs, jobs, nullptr, &n) == YMS_OK ? n : -1;
+  return conv_group<MODE_DGRAD>(njobs, jobs, nullptr, &n) == YMS_OK ? n : -1;
 }
 
 int yms_conv_dgrad_bnred_rows(const yms_conv_shape* s) {

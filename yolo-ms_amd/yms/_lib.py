@@ -8,7 +8,9 @@ libyms.so binds to the HIP runtime already loaded by torch (same soname).
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
+import types
 
 import torch  # noqa: F401  (loads the process' HIP runtime first)
 
@@ -217,51 +219,74 @@ def _elt(dt):
     return 4 if dt == F32 else 2
 
 
+# Solo entry points with a job record: their argument order before the stream, as fields of the record
+# ("dtype": the call's own): call_job unpacks a record by it, _work names a positional call's arguments.
+_ARGS = {k: v.split() for k, v in {
+    "yms_conv_fwd": "shape x x_ld x_off wpacked y y_ld y_off scale shift act res res_ld res_off stats",
+    "yms_conv_dgrad": "shape dz dz_ld dz_off wpacked_t dx dx_ld dx_off accumulate",
+    "yms_bn_finalize": "c stats rows stats_ld count gamma beta rmean rvar momentum eps mean_invstd scale shift",
+    "yms_bn_finalize_ld": "c stats rows stats_ld count gamma beta rmean rvar momentum eps mean_invstd mi_ld scale shift",
+    "yms_affine_act": "dtype npix c z z_ld z_off scale shift act res res_ld res_off out out_ld out_off",
+    "yms_bn_act_bwd_reduce": "dtype npix c z z_ld z_off gy gy_ld gy_off scale shift mean_invstd act ws",
+    "yms_bn_act_bwd_finalize": "c ws rows count dgamma dbeta coef",
+    "yms_bn_act_bwd_apply": "dtype npix c z z_ld z_off gy gy_ld gy_off scale shift mean_invstd coef act "
+                            "out out_ld out_off res res_ld res_off res_acc",
+    "yms_bias_bwd": "dtype npix c gy gy_ld gy_off ws counter dbias",
+}.items()}
+_JOB_ARGS = {k: operator.attrgetter(*[f for f in v if f != "dtype"]) for k, v in _ARGS.items()}
+
+
+def job_args(name, job, dtype=None):
+    """Solo entry point `name`'s arguments before the stream (ctypes passes a ConvShape field by address)."""
+    a = _JOB_ARGS[name](job)
+    return a if _ARGS[name][0] != "dtype" else (dtype,) + a
+
+
+def call_job(name, job, stream, dtype=None):
+    call(name, *job_args(name, job, dtype), stream)
+
+
 def _work(name, args):
     """(algorithmic FLOPs, algorithmic HBM bytes) of one launch: every operand read or written once.
     Convs: input + output + weights (fp32 weight gradient); depthwise: the same with fp32 [C][k][k]
     weights (FLOPs = 2 n h w c k^2, VALU); BN / branch-sum elementwise passes: their streams."""
     solo = _GROUP_AS.get(name)
-    if solo is not None:
-        fl = nb = 0
-        for j in args[-2][:args[-3]]:
-            if solo in _CONV:
-                a = (ctypes.pointer(j.shape),)
-            elif solo == "yms_affine_act":
-                a = (args[0], j.npix, j.c) + (None,) * 6 + (j.res,)
-            elif solo == "yms_bn_act_bwd_apply":
-                a = (args[0], j.npix, j.c) + (None,) * 14 + (j.res, None, None, j.res_acc)
-            elif solo == "yms_bn_act_bwd_reduce":
-                a = (args[0], j.npix, j.c)
-            else:
-                break
-            f, b = _work(solo, a)
-            fl, nb = fl + f, nb + b
-        return fl, nb
+    if solo is not None:             # the sum of the members, each priced as its solo call
+        works = [_work_job(solo, j, args[0]) for j in args[-2][:args[-3]]]
+        return sum(w[0] for w in works), sum(w[1] for w in works)
+    if name in _ARGS:
+        return _work_job(name, types.SimpleNamespace(**dict(zip(_ARGS[name], args))), args[0])
     if name in _CONV:
-        sh = args[0].contents
+        return _work_job(name, types.SimpleNamespace(shape=args[0]), None)
+    if name in _DW:
+        d = args[0].contents
+        vol = d.n * d.h * d.w * d.c
+        return 2 * vol * d.k * d.k, 2 * vol * _elt(d.dtype) + 4 * d.c * d.k * d.k
+    if name in ("yms_add_views", "yms_add_grad2"):
+        vol = args[1] * args[2] * _elt(args[0])
+        if name == "yms_add_views":
+            return 0, (2 + (args[6] is not None) + bool(args[12])) * vol
+        return 0, (3 + bool(args[9]) + bool(args[13])) * vol       # add_grad2: gy -> ga, gb
+    return 0, 0
+
+
+def _work_job(name, j, dtype):
+    """_work of solo entry point `name` from its arguments by name (dtype: its own first argument, if any)."""
+    if name in _CONV:
+        sh = getattr(j.shape, "contents", j.shape)     # a pointer (positional call) or the job's own shape
         fl = 2 * sh.n * sh.ho * sh.wo * sh.cout * sh.cin * sh.k * sh.k
         es = _elt(sh.dtype)
         act = (sh.n * sh.h * sh.w * sh.cin + sh.n * sh.ho * sh.wo * sh.cout) * es
         if name == "yms_conv_dgrad_bnred":             # + the producer's z at the dx pixels
             act += sh.n * sh.h * sh.w * sh.cin * es
         return fl, act + sh.cout * sh.cin * sh.k * sh.k * (4 if name == "yms_conv_wgrad" else es)
-    if name in _DW:
-        d = args[0].contents
-        vol = d.n * d.h * d.w * d.c
-        return 2 * vol * d.k * d.k, 2 * vol * _elt(d.dtype) + 4 * d.c * d.k * d.k
-    if name in ("yms_bn_act_bwd_reduce", "yms_affine_act", "yms_bn_act_bwd_apply", "yms_add_views",
-                "yms_add_grad2"):
-        vol = args[1] * args[2] * _elt(args[0])
-        if name == "yms_bn_act_bwd_reduce":
-            return 0, 2 * vol                                          # z, gy
-        if name == "yms_affine_act":
-            return 0, (2 + (args[9] is not None)) * vol                # z (+res) -> y
-        if name == "yms_bn_act_bwd_apply":
-            return 0, (3 + (args[17] is not None) * (1 + bool(args[20]))) * vol   # z, gy -> dz (+ gres)
-        if name == "yms_add_views":
-            return 0, (2 + (args[6] is not None) + bool(args[12])) * vol
-        return 0, (3 + bool(args[9]) + bool(args[13])) * vol       # add_grad2: gy -> ga, gb
+    vol = j.npix * j.c * _elt(dtype) if hasattr(j, "npix") else 0
+    if name == "yms_bn_act_bwd_reduce":
+        return 0, 2 * vol                                          # z, gy
+    if name == "yms_affine_act":
+        return 0, (2 + (j.res is not None)) * vol                  # z (+res) -> y
+    if name == "yms_bn_act_bwd_apply":
+        return 0, (3 + (j.res is not None) * (1 + bool(j.res_acc))) * vol   # z, gy -> dz (+ gres)
     return 0, 0
 
 

@@ -332,10 +332,19 @@ class ConvBase(Op):
         self.acc_res = T.write(self.res) if self.res is not None else 0
         self.acc_x = T.write(self.x) if self.x.buf.needs_grad else 0
 
-    def dgrad(self, rt, dz, ld, off):
+    def conv_job(self, rt, out, ld, off, sc, sh, act, res, stats):
+        """The conv into channels [off, off + c) of out, with scale / shift, act and residual in the
+        epilogue (eval) or the batch-statistics table into stats (training: the pre-BN output)."""
         x = self.x
-        L.call("yms_conv_dgrad", self.sp, dz, ld, off, rt.base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
-               self.acc_x, rt.st)
+        wp = rt.base + self.t_wp if rt.training else rt.eval_base + self.e_wp
+        return L.ConvFwdJob(self.shape, rt.a(x), x.buf.ld, x.off, wp, out, ld, off, sc, sh, act, *_opt(rt.a, res), stats)
+
+    def dgrad_job(self, rt, dz, ld, off):
+        x = self.x
+        return L.ConvDgradJob(self.shape, dz, ld, off, rt.base + self.t_wpt, rt.g(x), x.buf.ld, x.off, self.acc_x)
+
+    def dgrad(self, rt, dz, ld, off):
+        L.call_job("yms_conv_dgrad", self.dgrad_job(rt, dz, ld, off), rt.st)
 
     def launch_wgrad(self, rt, dz, ld, off, dw):
         x = self.x
@@ -405,55 +414,83 @@ class BNConvBase(ConvBase):
         # zero weight rows is NaN, so those z buffers start zeroed and their padding stays zero
         return [(self.z, self.npix * self.zld * es)] if self.zld != self.c else []
 
-    def fwd_train(self, rt):
-        """Each part's conv into its channels of z, with its batch statistics finalised (running
-        stats updated, scale / shift / (mean, invstd) written) before the next part reuses the
-        statistics scratch; then one affine + act (+ residual) pass z -> y."""
-        base, y = rt.base, self.y
-        stats = base + rt.plan.scratch["stats"]
-        z, sc, sh, mi = base + self.z, base + self.sc, base + self.sh, base + self.mi
-        for m, off in self.parts():
-            m.conv_fwd(rt, z, self.zld, off, None, None, L.ACT_NONE, None, stats)
-            bn = m.mod.bn
-            args = (m.c, stats, m.stats_rows, m.stats_ld, self.npix, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                    ctypes.c_float(bn.momentum if bn.momentum is not None else BN_MOMENTUM), ctypes.c_float(bn.eps))
-            if m is self:
-                L.call("yms_bn_finalize", *args, mi, sc, sh, rt.st)
-            else:           # a channel slot of this op's state: mean / invstd rows are self.c apart
-                L.call("yms_bn_finalize_ld", *args, mi + 4 * off, self.c, sc + 4 * off, sh + 4 * off, rt.st)
-        L.call("yms_affine_act", rt.plan.dt, self.npix, self.c, z, self.zld, 0, sc, sh, self.act,
-               *_opt(rt.a, self.res), rt.a(y), y.buf.ld, y.off, rt.st)
+    # ---- job records (include/yms.h) of this op's passes: its own fwd / bwd call the solo entry points
+    # with them, a HeadGroup collects its members' into grouped calls.  grp: as a member of a group, in the
+    # op's own slices (g_stats, g_bwd, g_coef: HeadGroup.layout) of the shared scratch regions.
+    def conv_args(self, rt, grp=False):
+        """(part, its conv_fwd / conv_job arguments) per conv: training into its channels of z with the
+        statistics table, eval into its output with the folded BN + act (+ residual) epilogue."""
+        if not rt.training:
+            eb = rt.eval_base
+            return [(m, (rt.a(m.y), m.y.buf.ld, m.y.off, eb + m.e_sc, eb + m.e_sh, m.act, m.res, None))
+                    for m, _ in self.parts()]
+        z, st = rt.base + self.z, rt.base + rt.plan.scratch["stats"]
+        return [(m, (z, self.zld, off, None, None, L.ACT_NONE, None, st + (m.g_stats if grp else 0)))
+                for m, off in self.parts()]
+
+    def finalize_jobs(self, rt, grp=False):
+        """Per part, into its channel slot of this op's state (mean / invstd rows are self.c apart)."""
+        st, sc, sh, mi = (rt.base + o for o in (rt.plan.scratch["stats"], self.sc, self.sh, self.mi))
+        return [L.BnFinalizeJob(m.c, st + (m.g_stats if grp else 0), m.stats_rows, m.stats_ld, self.npix,
+                                bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                                bn.running_var.data_ptr(), bn.momentum if bn.momentum is not None else BN_MOMENTUM,
+                                bn.eps, mi + 4 * off, self.c, sc + 4 * off, sh + 4 * off)
+                for m, off in self.parts() for bn in (m.mod.bn,)]
+
+    def pass_job(self, rt, **more):
+        """z, scale / shift and act, which the affine, reduce and apply passes share."""
+        base = rt.base
+        return L.BnPassJob(npix=self.npix, c=self.c, z=base + self.z, z_ld=self.zld, z_off=0, scale=base + self.sc,
+                           shift=base + self.sh, act=self.act, **more)
+
+    def affine_job(self, rt):
+        y = self.y
+        res, res_ld, res_off = _opt(rt.a, self.res)
+        return self.pass_job(rt, out=rt.a(y), out_ld=y.buf.ld, out_off=y.off, res=res, res_ld=res_ld, res_off=res_off)
+
+    def bwd_jobs(self, rt, dg, db, grp=False):
+        """-> the reduce, finalize (dgamma -> dg, dbeta -> db) and apply (dz over z, + the residual's
+        gradient) records.  The partial rows are the reduce pass's -- or already written by the consumer's
+        input gradient (bnred_by), its last writer, and the reduce record is not launched."""
+        y, gb, gs = self.y, rt.gbase, rt.plan.gscratch
+        coef = gb + gs["coef"] + (self.g_coef if grp else 0)
+        ws, rows = gb + gs["bwd"] + (self.g_bwd if grp else 0), self.bwd_rows
+        if self.bnred_by is not None:
+            ws, rows = gb + gs[self.bnred_key], self.bnred_rows
+        gy = dict(gy=rt.g(y), gy_ld=y.buf.ld, gy_off=y.off, mean_invstd=rt.base + self.mi)
+        res, res_ld, res_off = _opt(rt.g, self.res)
+        return (self.pass_job(rt, ws=ws, **gy), L.BnBwdFinalizeJob(self.c, ws, rows, self.npix, dg, db, coef),
+                self.pass_job(rt, coef=coef, out=rt.base + self.z, out_ld=self.zld, out_off=0, res=res, res_ld=res_ld,
+                              res_off=res_off, res_acc=self.acc_res, **gy))
+
+    def dz(self, rt):       # (address, channel stride, channel offset) of the output gradient after the apply pass
+        return rt.base + self.z, self.zld, 0
+
+    def bn_grads(self, rt):
+        return rt.pgrad(self.pg), rt.pgrad(self.pb)
 
     def fwd(self, rt):
-        if rt.training:
-            return self.fwd_train(rt)
-        y, eb = self.y, rt.eval_base      # eval: the folded BN + act (+ residual) in the conv's epilogue
-        self.conv_fwd(rt, rt.a(y), y.buf.ld, y.off, eb + self.e_sc, eb + self.e_sh, self.act, self.res, None)
+        """Training: each part's conv with its batch statistics finalised before the next part reuses the
+        statistics scratch, then one affine + act (+ residual) pass z -> y."""
+        fins = self.finalize_jobs(rt) if rt.training else ()
+        for i, (m, args) in enumerate(self.conv_args(rt)):
+            m.conv_fwd(rt, *args)
+            if fins:
+                L.call_job("yms_bn_finalize" if m is self else "yms_bn_finalize_ld", fins[i], rt.st)
+        if fins:
+            L.call_job("yms_affine_act", self.affine_job(rt), rt.st, rt.plan.dt)
 
-    def bn_bwd_sums(self, rt, dg, db):
-        """The BN + act backward's per-channel sums: partial rows by the reduce pass -- or already
-        written by the consumer's input gradient (bnred_by), its last writer -- then the finalize:
-        dgamma -> dg, dbeta -> db, the apply pass's coefficients -> the returned address."""
-        base, y, gs = rt.base, self.y, rt.plan.gscratch
-        if self.bnred_by is not None:
-            ws, rows = rt.gbase + gs[self.bnred_key], self.bnred_rows
-        else:
-            ws, rows = rt.gbase + gs["bwd"], self.bwd_rows
-            L.call("yms_bn_act_bwd_reduce", rt.plan.dt, self.npix, self.c, base + self.z, self.zld, 0, rt.g(y),
-                   y.buf.ld, y.off, base + self.sc, base + self.sh, base + self.mi, self.act, ws, rt.st)
-        coef = rt.gbase + gs["coef"]
-        L.call("yms_bn_act_bwd_finalize", self.c, ws, rows, self.npix, dg, db, coef, rt.st)
-        return coef
+    def bn_bwd(self, rt, dg, db):
+        """The reduce (unless bnred_by) and finalize passes -> the apply record, for bn_bwd_apply."""
+        red, fin, app = self.bwd_jobs(rt, dg, db)
+        if self.bnred_by is None:
+            L.call_job("yms_bn_act_bwd_reduce", red, rt.st, rt.plan.dt)
+        L.call_job("yms_bn_act_bwd_finalize", fin, rt.st)
+        return app
 
-    def bn_bwd_apply(self, rt, coef):
-        """dz written over z in place (+ the residual's gradient) -> dz's address."""
-        base, y = rt.base, self.y
-        z = base + self.z
-        L.call("yms_bn_act_bwd_apply", rt.plan.dt, self.npix, self.c, z, self.zld, 0, rt.g(y), y.buf.ld, y.off,
-               base + self.sc, base + self.sh, base + self.mi, coef, self.act, z, self.zld, 0,
-               *_opt(rt.g, self.res), self.acc_res, rt.st)
-        return z
+    def bn_bwd_apply(self, rt, app):
+        L.call_job("yms_bn_act_bwd_apply", app, rt.st, rt.plan.dt)
+        return self.dz(rt)
 
 
 class ConvOp(BNConvBase):
@@ -513,29 +550,22 @@ class ConvOp(BNConvBase):
         super().fwd(rt)
 
     def conv_fwd(self, rt, out, ld, off, sc, sh, act, res, stats):
-        """The conv into channels [off, off + c) of out, with scale / shift, act and residual in the
-        epilogue (eval) or the batch-statistics table into stats (training: the pre-BN output)."""
-        x = self.x
-        if self.stem_input is not None:
-            L.call("yms_conv_stem_fwd", self.sp, rt.stem_x[self.stem_input].data_ptr(), self.conv.weight.data_ptr(),
-                   out, ld, off, sc, sh, act, stats, self.stats_ld if stats else 0, rt.st)
-        else:
-            wp = rt.base + self.t_wp if rt.training else rt.eval_base + self.e_wp
-            L.call("yms_conv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, wp, out, ld, off, sc, sh, act,
-                   *_opt(rt.a, res), stats, rt.st)
+        if self.stem_input is None:
+            return L.call_job("yms_conv_fwd", self.conv_job(rt, out, ld, off, sc, sh, act, res, stats), rt.st)
+        L.call("yms_conv_stem_fwd", self.sp, rt.stem_x[self.stem_input].data_ptr(), self.conv.weight.data_ptr(),
+               out, ld, off, sc, sh, act, stats, self.stats_ld if stats else 0, rt.st)
 
     def dgrad(self, rt, dz, ld, off):
         q = self.bnred_for
         if q is None:
             return super().dgrad(rt, dz, ld, off)
         # + the producer's BN-backward reduce in the epilogue (dx = the producer's final gy)
-        x, base = self.x, rt.base
-        L.call("yms_conv_dgrad_bnred", self.sp, dz, ld, off, base + self.t_wpt, rt.g(x), x.buf.ld, x.off,
-               self.acc_x, base + q.z, q.zld, 0, base + q.sc, base + q.sh, base + q.mi, q.act,
-               rt.gbase + rt.plan.gscratch[self.bnred_wkey], rt.st)
+        base = rt.base
+        L.call("yms_conv_dgrad_bnred", *L.job_args("yms_conv_dgrad", self.dgrad_job(rt, dz, ld, off)), base + q.z,
+               q.zld, 0, base + q.sc, base + q.sh, base + q.mi, q.act, rt.gbase + rt.plan.gscratch[self.bnred_wkey], rt.st)
 
     def bwd(self, rt):
-        coef = self.bn_bwd_sums(rt, rt.pgrad(self.pg), rt.pgrad(self.pb))
+        app = self.bn_bwd(rt, *self.bn_grads(rt))
         if self.stem_input is not None:
             # the stem's input needs no gradient: the apply pass is fused into the weight
             # gradient, which reads gy, z and the NCHW input.
@@ -546,11 +576,10 @@ class ConvOp(BNConvBase):
             if dw is not None:
                 base, y = rt.base, self.y
                 L.call("yms_conv_stem_wgrad", self.sp, rt.stem_x[self.stem_input].data_ptr(), rt.g(y), y.buf.ld,
-                       y.off, base + self.z, self.zld, 0, base + self.sc, base + self.sh, base + self.mi, coef,
+                       y.off, base + self.z, self.zld, 0, base + self.sc, base + self.sh, base + self.mi, app.coef,
                        self.act, rt.gbase + rt.plan.gscratch["stemwg"], self.wg_ws, dw, 0, rt.st)
             return
-        dz = self.bn_bwd_apply(rt, coef)
-        self.bwd_grads(rt, dz, self.zld, 0, self.tail_wgrad_first)
+        self.bwd_grads(rt, *self.bn_bwd_apply(rt, app), self.tail_wgrad_first)
 
     def grad_params(self):
         return [self.pb, self.pg, self.pw]
@@ -628,13 +657,9 @@ class SiblingConvOp(BNConvBase):
         return [m.mod for m in self.members]
 
     def fwd(self, rt):
-        if not rt.training:
-            for m in self.members:      # eval: BN + act fused in each member's epilogue, into its slot
-                m.fwd(rt)
-            return
-        if not rt.prepacked:
+        if rt.training and not rt.prepacked:
             raise RuntimeError("yms: sibling convs need the batched pack (Plan.prepack)")
-        self.fwd_train(rt)
+        super().fwd(rt)             # (eval: BN + act fused in each member's epilogue, into its slot)
 
     def _adjacent(self, rt, attr):
         ps = [rt.pgrad(getattr(m, attr)) for m in self.members]
@@ -646,21 +671,23 @@ class SiblingConvOp(BNConvBase):
                 return None
         return ps[0]
 
+    def bn_grads(self, rt):
+        return self._adjacent(rt, "pg"), self._adjacent(rt, "pb")
+
     def bwd(self, rt):
         c = self.c
-        dg, db = self._adjacent(rt, "pg"), self._adjacent(rt, "pb")
+        dg, db = self.bn_grads(rt)
         if dg is not None and db is not None:
-            coef = self.bn_bwd_sums(rt, dg, db)
+            app = self.bn_bwd(rt, dg, db)
         else:
             tmp = rt.gbase + rt.plan.gscratch["sib"]
-            coef = self.bn_bwd_sums(rt, tmp, tmp + 4 * c)
+            app = self.bn_bwd(rt, tmp, tmp + 4 * c)
             for m, off in self.parts():
                 for src, pi in ((tmp, m.pg), (tmp + 4 * c, m.pb)):
                     d = rt.pgrad(pi)
                     if d is not None:
                         L.call("yms_copy", d, src + 4 * off, 4 * m.c, rt.st)
-        dz = self.bn_bwd_apply(rt, coef)
-        self.bwd_grads(rt, dz, self.zld, 0)
+        self.bwd_grads(rt, *self.bn_bwd_apply(rt, app))
 
     def wgrad(self, rt, dz, ld, off):
         dw = self._adjacent(rt, "pw")
@@ -704,24 +731,30 @@ class BiasConvOp(ConvBase):
     def eval_inputs(self):
         return [self.conv.weight]
 
+    def conv_args(self, rt, grp=False):
+        y = self.y
+        return [(self, (rt.a(y), y.buf.ld, y.off, None, self.conv.bias.data_ptr(), L.ACT_NONE, None, None))]
+
     def fwd(self, rt):
-        x, y = self.x, self.y
         if rt.training:
-            wp = rt.base + self.t_wp
             self.pack_unless_prepacked(rt)
-        else:
-            wp = rt.eval_base + self.e_wp
-        L.call("yms_conv_fwd", self.sp, rt.a(x), x.buf.ld, x.off, wp, rt.a(y), y.buf.ld, y.off,
-               None, self.conv.bias.data_ptr(), L.ACT_NONE, None, 0, 0, None, rt.st)
+        L.call_job("yms_conv_fwd", self.conv_job(rt, *self.conv_args(rt)[0][1]), rt.st)
+
+    def dz(self, rt):
+        y = self.y
+        return rt.g(y), y.buf.ld, y.off
+
+    def bias_job(self, rt, grp=False):
+        """dbias = the column sums of the output gradient (grp: as BNConvBase's job records)."""
+        gy, gy_ld, gy_off = self.dz(rt)
+        return L.BnPassJob(npix=self.npix, c=self.c, gy=gy, gy_ld=gy_ld, gy_off=gy_off,
+                           ws=rt.gbase + rt.plan.gscratch["bwd"] + (self.g_bwd if grp else 0),
+                           counter=rt.cnt(self.cnt), dbias=rt.pgrad(self.pbias))
 
     def bwd(self, rt):
-        y = self.y
-        gy, gyl, gyo = rt.g(y), y.buf.ld, y.off
-        db = rt.pgrad(self.pbias)
-        if db is not None:
-            L.call("yms_bias_bwd", rt.plan.dt, self.npix, self.c, gy, gyl, gyo,
-                   rt.gbase + rt.plan.gscratch["bwd"], rt.cnt(self.cnt), db, rt.st)
-        self.bwd_grads(rt, gy, gyl, gyo)
+        if rt.pgrad(self.pbias) is not None:
+            L.call_job("yms_bias_bwd", self.bias_job(rt), rt.st, rt.plan.dt)
+        self.bwd_grads(rt, *self.dz(rt))
 
     def grad_params(self):
         return [self.pbias, self.pw]
@@ -951,42 +984,14 @@ class HeadGroup:
         for st in self.stages:
             self.fwd_stage(rt, st)
 
-    @staticmethod
-    def conv_job(m, rt, wp, out, ld, off, sc, sh, act, res, stats):
-        x = m.x
-        return L.ConvFwdJob(m.shape, rt.a(x), x.buf.ld, x.off, wp, out, ld, off, sc, sh, act, *_opt(rt.a, res), stats)
-
     def fwd_stage(self, rt, st):
-        base, eb, dt = rt.base, rt.eval_base, rt.plan.dt
-        convs, fins, affs = [], [], []
-        for op in st:
-            y = op.y
-            if isinstance(op, BiasConvOp):
-                wp = base + op.t_wp if rt.training else eb + op.e_wp
-                convs.append(self.conv_job(op, rt, wp, rt.a(y), y.buf.ld, y.off, None, op.conv.bias.data_ptr(),
-                                           L.ACT_NONE, None, None))
-            elif not rt.training:
-                for m in (op.members if isinstance(op, SiblingConvOp) else (op,)):
-                    convs.append(self.conv_job(m, rt, eb + m.e_wp, rt.a(m.y), m.y.buf.ld, m.y.off, eb + m.e_sc,
-                                               eb + m.e_sh, m.act, m.res, None))
-            else:
-                z, sc, sh, mi = base + op.z, base + op.sc, base + op.sh, base + op.mi
-                for m, off in op.parts():
-                    stats = base + rt.plan.scratch["stats"] + m.g_stats
-                    convs.append(self.conv_job(m, rt, base + m.t_wp, z, op.zld, off, None, None, L.ACT_NONE, None, stats))
-                    bn = m.mod.bn
-                    fins.append(L.BnFinalizeJob(m.c, stats, m.stats_rows, m.stats_ld, op.npix, bn.weight.data_ptr(),
-                                                bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                                                bn.running_var.data_ptr(),
-                                                bn.momentum if bn.momentum is not None else BN_MOMENTUM, bn.eps,
-                                                mi + 4 * off, op.c, sc + 4 * off, sh + 4 * off))
-                affs.append(L.BnPassJob(npix=op.npix, c=op.c, z=z, z_ld=op.zld, z_off=0, scale=sc, shift=sh,
-                                        act=op.act, out=rt.a(y), out_ld=y.buf.ld, out_off=y.off,
-                                        **dict(zip(("res", "res_ld", "res_off"), _opt(rt.a, op.res)))))
+        convs = [m.conv_job(rt, *args) for op in st for m, args in op.conv_args(rt, True)]
         L.call("yms_conv_fwd_group", len(convs), _array(convs), rt.st)
-        if fins:
+        bn = [op for op in st if rt.training and isinstance(op, BNConvBase)]
+        if bn:
+            fins = [j for op in bn for j in op.finalize_jobs(rt, True)]
             L.call("yms_bn_finalize_group", len(fins), _array(fins), rt.st)
-            L.call("yms_affine_act_group", dt, len(affs), _array(affs), rt.st)
+            L.call("yms_affine_act_group", rt.plan.dt, len(bn), _array([op.affine_job(rt) for op in bn]), rt.st)
 
     # ---- backward ------------------------------------------------------------------------
     def bwd_grouped(self, rt):
@@ -1011,46 +1016,21 @@ class HeadGroup:
             self.bwd_stage(rt, st[::-1])
 
     def bwd_stage(self, rt, ops):
-        base, gb, gs, dt = rt.base, rt.gbase, rt.plan.gscratch, rt.plan.dt
-        dzs = {}      # op -> (address, channel stride, channel offset) of its output gradient dz
-        bias, red, fin, app = [], [], [], []
-        for op in ops:
-            y = op.y
-            gy, gyl, gyo = rt.g(y), y.buf.ld, y.off
-            ws = gb + gs["bwd"] + op.g_bwd
-            if isinstance(op, BiasConvOp):
-                bias.append(L.BnPassJob(npix=op.npix, c=op.c, gy=gy, gy_ld=gyl, gy_off=gyo, ws=ws,
-                                        counter=rt.cnt(op.cnt), dbias=rt.pgrad(op.pbias)))
-                dzs[id(op)] = (gy, gyl, gyo)
-                continue
-            z, coef = base + op.z, gb + gs["coef"] + op.g_coef
-            common = dict(npix=op.npix, c=op.c, z=z, z_ld=op.zld, z_off=0, gy=gy, gy_ld=gyl, gy_off=gyo,
-                          scale=base + op.sc, shift=base + op.sh, mean_invstd=base + op.mi, act=op.act)
-            red.append(L.BnPassJob(ws=ws, **common))
-            if isinstance(op, SiblingConvOp):
-                dg, db = op._adjacent(rt, "pg"), op._adjacent(rt, "pb")
-            else:
-                dg, db = rt.pgrad(op.pg), rt.pgrad(op.pb)
-            fin.append(L.BnBwdFinalizeJob(op.c, ws, op.bwd_rows, op.npix, dg, db, coef))
-            res, res_ld, res_off = _opt(rt.g, op.res)
-            app.append(L.BnPassJob(coef=coef, out=z, out_ld=op.zld, out_off=0, res=res, res_ld=res_ld,
-                                   res_off=res_off, res_acc=op.acc_res, **common))
-            dzs[id(op)] = (z, op.zld, 0)
+        dt = rt.plan.dt
+        bias = [op.bias_job(rt, True) for op in ops if isinstance(op, BiasConvOp)]
         if bias:
             L.call("yms_bias_bwd_group", dt, len(bias), _array(bias), rt.st)
-        if red:
+        bn = [op.bwd_jobs(rt, *op.bn_grads(rt), True) for op in ops if isinstance(op, BNConvBase)]
+        if bn:
+            red, fin, app = zip(*bn)
             L.call("yms_bn_act_bwd_reduce_group", dt, len(red), _array(red), rt.st)
             L.call("yms_bn_act_bwd_finalize_group", len(fin), _array(fin), rt.st)
             L.call("yms_bn_act_bwd_apply_group", dt, len(app), _array(app), rt.st)
-        dgs = []
-        for op in ops:
-            x = op.x
-            if x.buf.needs_grad:
-                dgs.append(L.ConvDgradJob(op.shape, *dzs[id(op)], base + op.t_wpt, rt.g(x), x.buf.ld, x.off, op.acc_x))
+        dgs = [op.dgrad_job(rt, *op.dz(rt)) for op in ops if op.x.buf.needs_grad]
         if dgs:
             L.call("yms_conv_dgrad_group", len(dgs), _array(dgs), rt.st)
         for op in ops:
-            op.wgrad(rt, *dzs[id(op)])
+            op.wgrad(rt, *op.dz(rt))
 
 
 HeadGroup.KINDS = (ConvOp, SiblingConvOp, BiasConvOp)
