@@ -6,7 +6,14 @@ foreground), GTs of different classes sharing anchors (overwritten boxes, accumu
 every IoU variant, BCE pos_weight, bf16 maps, the full 640x640 anchor grid at nc = 80.  The
 restatement is pinned bit-for-bit to the reference's own ComputeLoss by the fixtures of
 tests/golden/make_loss_golden.py (tests/test_loss_golden.py); test_loss_vs_reference_fixtures checks
-the GPU kernels against those fixtures directly."""
+the GPU kernels against those fixtures directly.
+
+These cases compare one relative L2 norm per level at the training weights and never exceed 16
+target rows or 3 images.  tests/test_loss_edges_gpu.py (inputs: tests/loss_cases.py) covers what
+that leaves out: each loss term's gradient on its own, per (image, level) block; hundreds and
+thousands of target rows (assign_kernel's staging rounds and its unstaged scan); 65 and 260 images;
+1 and 4 levels, 5 anchors; nc = 1 / 33 / 80 class words; exact top-k ties; the DFL bin edges; f16
+and bf16 everywhere; wider buffers, need_grad=False and run-to-run determinism."""
 import numpy as np
 import pytest
 import torch
