@@ -23,6 +23,10 @@
  *   yms_head_decode         yolov8_head.py:127-158 make_anchors + DFL (components.py:162-191)
  *   yms_nms_*               train.py:63-113 / tools/test.py:166-218 post-process and the
  *                           torchvision.ops.nms(boxes, scores, iou) call at train.py:93
+ *   yms_resize_normalize,   tools/dataset.py:84-134 transform list + collate_fn's stack (:260)
+ *   yms_augment_normalize
+ *   yms_mosaic_normalize    the config's `mosaic` / `mixup` keys, which dataset.py never reads:
+ *                           YOLOv5 load_mosaic / random_perspective / mixup semantics, opt-in
  */
 #ifndef YMS_H
 #define YMS_H
@@ -384,6 +388,19 @@ yms_status yms_resize_normalize(int dtype, int n, const void* images, int out_h,
 size_t yms_augment_image_bytes(void);
 yms_status yms_augment_normalize(int dtype, int n, const void* images, int out_h, int out_w, const float* mean,
                                  const float* std, void* out, void* stream);
+/* Mosaic and MixUp (YOLOv5 load_mosaic / random_perspective / mixup, restated; opt-in through
+ * yms.data.COCODataset(mosaic=True)), batched: records = device array of n MosImage records
+ * (yms_mosaic_image_bytes() bytes each; layout in csrc/preprocess.hip / yms.data.MosImage).  A record
+ * is one output image: one or two layers and the MixUp weight r (pixel = b + r * (a - b) before
+ * Normalize).  A layer holds a fill value (the canvas background and the constant border), an HSV
+ * shift, up to 8 stages with yms_augment_normalize's meaning that end on the canvas, and one to four
+ * tiles { src, h, w, pitch, canvas rect, sx, sy, tx, ty }: the canvas coordinate picks the tile whose
+ * rect holds its rounded value and samples that tile's source once at (sx * x + tx, sy * y + ty),
+ * clamped into the image.  A plain AugImage is the layer with fill 0 and one identity tile, for which
+ * the output equals yms_augment_normalize's bit for bit, so mixed batches are one launch. */
+size_t yms_mosaic_image_bytes(void);
+yms_status yms_mosaic_normalize(int dtype, int n, const void* records, int out_h, int out_w, const float* mean,
+                                const float* std, void* out, void* stream);
 
 /* ---- detection loss ------------------------------------------------------- */
 /* The reference's ComputeLoss (yolov8/tools/loss.py:94-677; python binding

@@ -24,6 +24,11 @@ per transform); ``transform_boxes`` moves the COCO boxes through the same stages
 envelopes, clipped once at the end, then the visibility / area filters).  albumentations and cv2
 are not installed, so parity with them is UNPINNED; the GPU kernel is pinned
 to the restatement in oracle/preprocess_ref.py.
+
+Mosaic and MixUp (the config's ``mosaic`` / ``mixup`` keys, which the reference's transform list
+never reads) are opt-in through ``COCODataset(..., mosaic=True)``: YOLOv5's semantics restated,
+sampled on the host (``sample_mosaic``, ``mosaic_boxes``) and composed on the GPU in one launch
+(``mosaic_normalize``); see the section below.
 """
 from __future__ import annotations
 
@@ -215,6 +220,15 @@ def sample_augmentation(rng, tp, h, w, out_h, out_w, is_train=True):
     return plan
 
 
+def _fill_stages(st, stages):
+    """AugStage records (output -> input frame, the inverse of each forward map) of a plan's stages."""
+    for k, (F, in_w, in_h, _, _, border) in enumerate(stages):
+        M = np.linalg.inv(F)
+        M = M / M[2, 2] if abs(M[2, 2]) > 1e-12 else M
+        st[k].m[:] = [float(v) for v in M.reshape(-1)]
+        st[k].in_w, st[k].in_h, st[k].border = in_w, in_h, border
+
+
 def plan_struct(plan, image):
     """AugImage record of one plan over a device HWC uint8 image tensor."""
     rec = AugImage()
@@ -226,11 +240,7 @@ def plan_struct(plan, image):
     if plan.hsv is not None:
         rec.do_hsv = 1
         rec.hsv[:] = [float(v) for v in plan.hsv]
-    for k, (F, in_w, in_h, _, _, border) in enumerate(plan.stages):
-        M = np.linalg.inv(F)
-        M = M / M[2, 2] if abs(M[2, 2]) > 1e-12 else M
-        rec.st[k].m[:] = [float(v) for v in M.reshape(-1)]
-        rec.st[k].in_w, rec.st[k].in_h, rec.st[k].border = in_w, in_h, border
+    _fill_stages(rec.st, plan.stages)
     return rec
 
 
@@ -320,6 +330,282 @@ def coco_boxes_to_targets(boxes, labels, img_w, img_h, out_w, out_h):
     return torch.tensor(rows, dtype=torch.float32) if rows else torch.empty(0, 5)
 
 
+# ------------------------------------------------------------------------------------------
+# Mosaic and MixUp (opt-in; the published YOLOv5 load_mosaic / random_perspective / mixup, restated)
+# ------------------------------------------------------------------------------------------
+# The reference's config carries ``mosaic`` and ``mixup`` but its transform list never reads them,
+# so the semantics are YOLOv5's.  One LAYER is a canvas of 2W x 2H pixels filled with 114, a centre
+# (xc, yc), and four letterbox-resized TILES anchored at the centre (TL's bottom-right corner, TR's
+# bottom-left, BL's top-right, BR's top-left) and cropped by the canvas edge only; then ONE
+# constant-border stage canvas -> output (M = T S R P C, the border drawn in the fill), the flips
+# and the HSV shift (applied to the fill too).  MixUp blends two independent layers,
+# b + r (a - b) with r ~ Beta(32, 32), and concatenates their targets.  The GPU evaluates a record
+# in one launch (csrc/preprocess.hip mosaic_normalize_kernel): the stage walk of augment_normalize
+# plus the tile choice, one bilinear sample of one source per layer.  ultralytics and cv2 are not
+# installed: parity with them is UNPINNED; the kernel is pinned to tests/mosaic_ref.py.
+MOS_MAX_TILES, MOS_MAX_LAYERS = 4, 2
+MOSAIC_FILL = 114.0
+
+
+class MosTile(ctypes.Structure):
+    """One tile: the source image, its canvas rect [x0, x1) x [y0, y1) and the map from a canvas pixel
+    index to a source pixel index, xs = sx * x + tx."""
+    _fields_ = [("src", ctypes.c_void_p), ("h", ctypes.c_int), ("w", ctypes.c_int), ("pitch", ctypes.c_int),
+                ("pad_", ctypes.c_int), ("x0", ctypes.c_int), ("y0", ctypes.c_int), ("x1", ctypes.c_int),
+                ("y1", ctypes.c_int), ("sx", ctypes.c_float), ("sy", ctypes.c_float), ("tx", ctypes.c_float),
+                ("ty", ctypes.c_float)]
+
+
+class MosLayer(ctypes.Structure):
+    """do_hsv: bit 0 shifts the taps, bit 1 the fill."""
+    _fields_ = [("fill", ctypes.c_float), ("nst", ctypes.c_int), ("ntile", ctypes.c_int), ("do_hsv", ctypes.c_int),
+                ("hsv", ctypes.c_float * 3), ("pad_", ctypes.c_int), ("st", AugStage * AUG_MAX_STAGES),
+                ("tile", MosTile * MOS_MAX_TILES)]
+
+
+class MosImage(ctypes.Structure):
+    """csrc/preprocess.hip MosImage (checked against yms_mosaic_image_bytes()): one output image."""
+    _fields_ = [("nlayer", ctypes.c_int), ("r", ctypes.c_float), ("layer", MosLayer * MOS_MAX_LAYERS)]
+
+
+class MosaicTile:
+    """Source ``src`` (index into the sample's image list, h x w pixels) resized to nw x nh with its
+    column 0 / row 0 at canvas (ox, oy) -- possibly negative -- and visible in ``rect`` = (x0, y0, x1, y1)."""
+
+    def __init__(self, src, h, w, nw, nh, ox, oy, rect):
+        self.src, self.h, self.w, self.nw, self.nh, self.ox, self.oy = src, h, w, nw, nh, ox, oy
+        self.rect = tuple(int(v) for v in rect)
+
+    @property
+    def map(self):
+        """(sx, sy, tx, ty) in float64: the resize's half-pixel rule, canvas index -> source index."""
+        sx, sy = self.w / self.nw, self.h / self.nh
+        return sx, sy, (0.5 - self.ox) * sx - 0.5, (0.5 - self.oy) * sy - 0.5
+
+
+class MosaicLayer(AugPlan):
+    """One mosaic layer: an AugPlan whose source frame is the canvas (stages, hsv and ``applied`` as
+    there), plus the canvas fill, the centre and the tiles in TL, TR, BL, BR order."""
+
+    def __init__(self, canvas_h, canvas_w, fill=MOSAIC_FILL):
+        super().__init__(canvas_h, canvas_w)
+        self.fill = float(fill)
+        self.center = None
+        self.tiles = []
+
+
+class MosaicPlan:
+    """One output image: one layer (Mosaic) or two (MixUp, ``r`` the weight of layer 0) over the
+    sample's image list; ``applied`` names what was drawn (diagnostics / tests)."""
+
+    def __init__(self, layers, r=1.0):
+        self.layers = list(layers)
+        self.r = float(r)
+        if not 1 <= len(self.layers) <= MOS_MAX_LAYERS:
+            raise ValueError("yms: a MosaicPlan has one or two layers")
+
+    @property
+    def applied(self):
+        return ["mosaic"] + (["mixup"] if len(self.layers) > 1 else []) + [a for ly in self.layers for a in ly.applied]
+
+    @property
+    def frame(self):
+        return self.layers[0].frame
+
+
+def mosaic_tiles(sizes, xc, yc, out_h, out_w):
+    """The four tiles of sources ``sizes`` = [(h0, w0)] x 4 (TL, TR, BL, BR) about the centre (xc, yc)."""
+    tiles = []
+    for k, (h0, w0) in enumerate(sizes):
+        r = min(out_w / w0, out_h / h0)
+        nw, nh = max(1, round(w0 * r)), max(1, round(h0 * r))
+        ox = xc - nw if k in (0, 2) else xc
+        oy = yc - nh if k in (0, 1) else yc
+        rect = (max(ox, 0), max(oy, 0), min(ox + nw, 2 * out_w), min(oy + nh, 2 * out_h))
+        tiles.append(MosaicTile(k, h0, w0, nw, nh, ox, oy, rect))
+    return tiles
+
+
+def sample_mosaic(rng, tp, sizes, out_h, out_w, center=None):
+    """One mosaic layer over four sources of ``sizes`` = [(h, w)] x 4 for an out_h x out_w output.
+    Draws from the numpy Generator ``rng``, in this order (every uniform is drawn even where its
+    limit is 0, so the stream does not depend on the config):
+      1. xc = int(U(W/2, 3W/2)), yc = int(U(H/2, 3H/2))   (``center`` overrides them after the draw);
+      2. one permutation of 0..3: position TL, TR, BL, BR gets source perm[position];
+      3. perspective P[2,0], P[2,1] ~ U(-perspective, perspective);
+      4. rotation angle ~ U(-degrees, degrees), gain ~ U(1 - scale, 1 + scale);
+      5. shear S[0,1], S[1,0] = tan(U(-shear, shear) degrees);
+      6. translation U(0.5 - translate, 0.5 + translate) * W, then * H;
+      7. the flips, then the HSV shift, each exactly as sample_augmentation draws them.
+    The canvas stage's forward matrix is T S R P C with C the translation by (-W, -H)."""
+    tp = tp or {}
+    W, H = int(out_w), int(out_h)
+    ly = MosaicLayer(2 * H, 2 * W)
+    xc, yc = int(rng.uniform(W / 2, 3 * W / 2)), int(rng.uniform(H / 2, 3 * H / 2))
+    if center is not None:
+        xc, yc = (int(v) for v in center)
+    ly.center = (xc, yc)
+    perm = [int(v) for v in rng.permutation(4)]
+    ly.tiles = mosaic_tiles([sizes[k] for k in perm], xc, yc, H, W)
+    for t, k in zip(ly.tiles, perm):
+        t.src = k
+    C = np.array([[1, 0, -W], [0, 1, -H], [0, 0, 1]], np.float64)
+    p = tp.get("perspective", 0)
+    P = np.eye(3)
+    P[2, 0], P[2, 1] = rng.uniform(-p, p), rng.uniform(-p, p)
+    deg, sc = tp.get("degrees", 0), tp.get("scale", 0)
+    ang = rng.uniform(-deg, deg)
+    R = _rot_matrix(0, 0, ang, rng.uniform(1 - sc, 1 + sc))
+    sh = tp.get("shear", 0)
+    S = np.eye(3)
+    S[0, 1] = np.tan(np.deg2rad(rng.uniform(-sh, sh)))
+    S[1, 0] = np.tan(np.deg2rad(rng.uniform(-sh, sh)))
+    tr = tp.get("translate", 0)
+    T = np.eye(3)
+    T[0, 2] = rng.uniform(0.5 - tr, 0.5 + tr) * W
+    T[1, 2] = rng.uniform(0.5 - tr, 0.5 + tr) * H
+    ly.add(T @ S @ R @ P @ C, W, H, AUG_CONSTANT, "affine")
+    if p > 0:
+        ly.applied.append("perspective")
+    if tp.get("fliplr", 0) > 0 and rng.random() < tp["fliplr"]:
+        ly.add(np.array([[-1, 0, W - 1], [0, 1, 0], [0, 0, 1]]), W, H, AUG_CLAMP, "fliplr")
+    if tp.get("flipud", 0) > 0 and rng.random() < tp["flipud"]:
+        ly.add(np.array([[1, 0, 0], [0, -1, H - 1], [0, 0, 1]]), W, H, AUG_CLAMP, "flipud")
+    hl, sl, vl = (int(tp.get(k, 0) * 100) for k in ("hsv_h", "hsv_s", "hsv_v"))
+    if tp.get("hsv_h", 0) > 0 or tp.get("hsv_s", 0) > 0 or tp.get("hsv_v", 0) > 0:
+        if rng.random() < 0.5:
+            ly.hsv = (rng.uniform(-hl, hl), rng.uniform(-sl, sl), rng.uniform(-vl, vl))
+            ly.applied.append("hsv")
+    return ly
+
+
+def _envelope(P, stages):
+    """Corner envelope (x0, y0, x1, y1) of continuous-coordinate corners P [4, 2] after the stages."""
+    P = np.asarray(P, np.float64) - 0.5
+    for F, *_ in stages:
+        q = np.c_[P, np.ones(4)] @ F.T
+        P = q[:, :2] / q[:, 2:3]
+    P = P + 0.5
+    return (*P.min(0), *P.max(0))
+
+
+def _corners(x0, y0, x1, y1):
+    return [[x0, y0], [x1, y0], [x1, y1], [x0, y1]]
+
+
+def mosaic_boxes(layer, annotations, min_visibility=0.1, min_area=1.0):
+    """[n, 5] targets (class, cx, cy, w, h normalised to the output) of one layer.  annotations:
+    per image of the sample's list, (COCO [x, y, w, h] pixel boxes, labels).  Each box of a tile's
+    source is mapped to the canvas through the tile's resize, intersected with the tile's rect (and
+    dropped if nothing is left); the clipped AND the unclipped canvas box go through the canvas stages
+    as corner envelopes, the clipped one is then clipped to the output frame, and transform_boxes'
+    filters apply with the unclipped envelope as the visibility's denominator."""
+    out_w, out_h = layer.frame
+    rows = []
+    for t in layer.tiles:
+        boxes, labels = annotations[t.src]
+        gx, gy = t.nw / t.w, t.nh / t.h
+        rx0, ry0, rx1, ry1 = t.rect
+        for (x, y, w, h), c in zip(boxes, labels):
+            u = (t.ox + x * gx, t.oy + y * gy, t.ox + (x + w) * gx, t.oy + (y + h) * gy)
+            k = (max(u[0], rx0), max(u[1], ry0), min(u[2], rx1), min(u[3], ry1))
+            if k[2] <= k[0] or k[3] <= k[1]:
+                continue
+            ux0, uy0, ux1, uy1 = _envelope(_corners(*u), layer.stages)
+            x0, y0, x1, y1 = _envelope(_corners(*k), layer.stages)
+            area = (ux1 - ux0) * (uy1 - uy0)
+            cx0, cy0 = min(max(x0, 0.0), out_w), min(max(y0, 0.0), out_h)
+            cx1, cy1 = min(max(x1, 0.0), out_w), min(max(y1, 0.0), out_h)
+            carea = max(cx1 - cx0, 0.0) * max(cy1 - cy0, 0.0)
+            if area <= 0 or carea / area < min_visibility or carea < min_area:
+                continue
+            bw, bh = cx1 - cx0, cy1 - cy0
+            cxn, cyn, wn, hn = (cx0 + bw / 2) / out_w, (cy0 + bh / 2) / out_h, bw / out_w, bh / out_h
+            if wn > 1e-3 and hn > 1e-3 and 0 <= cxn <= 1 and 0 <= cyn <= 1 and 0 <= wn <= 1 and 0 <= hn <= 1:
+                rows.append([c, cxn, cyn, wn, hn])
+    return torch.tensor(rows, dtype=torch.float32) if rows else torch.empty(0, 5)
+
+
+def mosaic_targets(plan, annotations):
+    """The plan's targets: its layers' mosaic_boxes, concatenated."""
+    return torch.cat([mosaic_boxes(ly, annotations) for ly in plan.layers], 0)
+
+
+def _check_image(im, dev=None):
+    if (dev is not None and im.device != dev) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 \
+            or im.stride(2) != 1 or im.stride(1) != 3:
+        raise ValueError("yms: images must be contiguous HWC uint8 RGB tensors on one device")
+
+
+def mosaic_struct(plan, images):
+    """MosImage record of a MosaicPlan over its sample's device image list -- or of a plain AugPlan
+    over its one image, as the degenerate layer: fill 0, no HSV on the fill, one tile that is the
+    source itself (rect = stage 0's input frame, identity map)."""
+    rec = MosImage()
+    if isinstance(plan, MosaicPlan):
+        layers = plan.layers
+        rec.r = plan.r
+    else:
+        image = images[0] if isinstance(images, (list, tuple)) else images
+        if tuple(image.shape[:2]) != (plan.src_h, plan.src_w):
+            raise ValueError("yms: augmentation plan sampled for another image size")
+        ly = MosaicLayer(plan.src_h, plan.src_w, fill=0.0)
+        ly.hsv, ly.stages = plan.hsv, plan.stages
+        ly.tiles = [MosaicTile(0, plan.src_h, plan.src_w, plan.src_w, plan.src_h, 0, 0,
+                               (0, 0, plan.src_w, plan.src_h))]
+        layers, images = [ly], [image]
+        rec.r = 1.0
+    rec.nlayer = len(layers)
+    for lr, ly in zip(rec.layer, layers):
+        if len(ly.stages) > AUG_MAX_STAGES or not 1 <= len(ly.tiles) <= MOS_MAX_TILES:
+            raise ValueError("yms: a layer has at most AUG_MAX_STAGES stages and one to four tiles")
+        lr.fill, lr.nst, lr.ntile = ly.fill, len(ly.stages), len(ly.tiles)
+        if ly.hsv is not None:
+            lr.do_hsv = 3 if isinstance(plan, MosaicPlan) else 1
+            lr.hsv[:] = [float(v) for v in ly.hsv]
+        _fill_stages(lr.st, ly.stages)
+        for tr, t in zip(lr.tile, ly.tiles):
+            im = images[t.src]
+            if tuple(im.shape[:2]) != (t.h, t.w):
+                raise ValueError("yms: mosaic tile sampled for another image size")
+            tr.src, tr.h, tr.w, tr.pitch = im.data_ptr(), t.h, t.w, im.stride(0)
+            tr.x0, tr.y0, tr.x1, tr.y1 = t.rect
+            tr.sx, tr.sy, tr.tx, tr.ty = t.map
+    return rec
+
+
+def mosaic_normalize(images, plans, size, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype=torch.float32):
+    """One launch (yms_mosaic_normalize) for a batch of mosaic and plain samples -> [B, 3, H, W].
+    images[i]: the device image list of MosaicPlan plans[i], or the one device image of a plain
+    AugPlan (expressed as the degenerate record, for which the output is augment_normalize's)."""
+    if not images or len(images) != len(plans):
+        raise ValueError("yms: one plan per sample")
+    samples = [list(im) if isinstance(im, (list, tuple)) else [im] for im in images]
+    dev = samples[0][0].device
+    if dev.type != "cuda":
+        raise RuntimeError("yms: mosaic_normalize runs on ROCm GPU tensors only (no CPU fallback)")
+    if L.lib().yms_mosaic_image_bytes() != ctypes.sizeof(MosImage):
+        raise RuntimeError("yms: MosImage layout differs from the library's")
+    H, W = size
+    n = len(samples)
+    tab = (MosImage * n)()
+    for i, (ims, pl) in enumerate(zip(samples, plans)):
+        for im in ims:
+            _check_image(im, dev)
+        if pl.frame != (W, H):
+            raise ValueError("yms: plan does not produce the batch size")
+        tab[i] = mosaic_struct(pl, ims)
+    tab_dev = torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev, non_blocking=False)
+    out = torch.empty((n, 3, H, W), dtype=dtype, device=dev)
+    L.call("yms_mosaic_normalize", L.dtype_code(dtype), n, tab_dev.data_ptr(), H, W,
+           (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), out.data_ptr(), L.stream_ptr(dev))
+    for ims in samples:
+        for im in ims:
+            im.record_stream(torch.cuda.current_stream(dev))
+    tab_dev.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
 class COCODetection(torch.utils.data.Dataset):
     """dataset.py COCODataset's data source (image list, category map, annotation filters) without
     pycocotools; ``__getitem__`` returns (decoded HWC uint8 image, [n, 5] targets for ``img_size``),
@@ -403,32 +689,71 @@ class COCODataset(COCODetection):
     ``transform_params`` (the config's ``augmentation`` dict) is sampled per sample on the host
     (``sample_augmentation``) and applied on the GPU by the collate (``collate_to_gpu``);
     ``is_train=False`` keeps only the Resize.  ``__getitem__`` -> (decoded HWC uint8 image,
-    [n, 5] targets in the augmented frame, AugPlan)."""
+    [n, 5] targets in the augmented frame, AugPlan).
+
+    ``mosaic=True`` opts into Mosaic / MixUp (training only): ``transform_params["mosaic"]`` and
+    ``["mixup"]`` are then probabilities.  A sample's first draw decides Mosaic (no draw when the
+    probability is 0); a mosaic sample draws three more dataset indices (uniform, repeats allowed),
+    its layer (``sample_mosaic``), then decides MixUp (no draw when its probability is 0), which
+    draws four indices, a second independent layer and r ~ Beta(32, 32).  ``__getitem__`` returns
+    (list of decoded images, [n, 5] targets, MosaicPlan) for such a sample and the plain tuple
+    otherwise, drawn from the same generator after the decision.  With ``mosaic=False`` (the
+    default) both keys are ignored and no extra number is drawn.  ``ds.mosaic`` may be set at any
+    time, e.g. to close Mosaic for the last epochs -- but DataLoader workers hold copies of the
+    dataset made when their iterator started (with ``persistent_workers=True`` for the whole run),
+    so a change reaches them only through a new iterator / DataLoader."""
 
     def __init__(self, images_dir, annotations_file, transform_params=None, is_train=True, img_size=(640, 640),
-                 num_classes=80, seed=0):
+                 num_classes=80, seed=0, mosaic=False):
         super().__init__(images_dir, annotations_file, img_size=img_size, num_classes=num_classes, seed=seed)
         self.transform_params = dict(transform_params or {})
         self.is_train = is_train
+        self.mosaic = mosaic
+
+    def _load(self, idx):
+        from PIL import Image
+        info = self.imgs[self.image_ids[idx]]
+        image = np.array(Image.open(os.path.join(self.images_dir, info["file_name"])).convert("RGB"))
+        return image, self.annotations(idx)
+
+    def _mosaic_layer(self, rng, idxs, images, anns):
+        """One layer over dataset indices ``idxs``, its sources appended to the sample's lists."""
+        base = len(images)
+        for i in idxs:
+            im, an = self._load(int(i))
+            images.append(im)
+            anns.append(an)
+        ly = sample_mosaic(rng, self.transform_params, [im.shape[:2] for im in images[base:]], self.img_h, self.img_w)
+        for t in ly.tiles:
+            t.src += base
+        return ly
 
     def __getitem__(self, idx):
-        from PIL import Image
         if torch.is_tensor(idx):
             idx = idx.item()
         if not isinstance(idx, int):
             raise TypeError(f"Index should be an integer, got {type(idx).__name__} instead.")
-        info = self.imgs[self.image_ids[idx]]
-        image = np.array(Image.open(os.path.join(self.images_dir, info["file_name"])).convert("RGB"))
-        boxes, labels = self.annotations(idx)
+        rng = self.sample_rng(idx)
+        tp = self.transform_params
+        if self.mosaic and self.is_train and tp.get("mosaic", 0) > 0 and rng.random() < tp["mosaic"]:
+            images, anns = [], []
+            layers = [self._mosaic_layer(rng, [idx, *rng.integers(0, len(self), 3)], images, anns)]
+            r = 1.0
+            if tp.get("mixup", 0) > 0 and rng.random() < tp["mixup"]:
+                layers.append(self._mosaic_layer(rng, rng.integers(0, len(self), 4), images, anns))
+                r = rng.beta(32.0, 32.0)
+            plan = MosaicPlan(layers, r)
+            return images, mosaic_targets(plan, anns), plan
+        image, (boxes, labels) = self._load(idx)
         h0, w0 = image.shape[:2]
-        plan = sample_augmentation(self.sample_rng(idx), self.transform_params, h0, w0, self.img_h, self.img_w,
-                                   self.is_train)
+        plan = sample_augmentation(rng, tp, h0, w0, self.img_h, self.img_w, self.is_train)
         return image, transform_boxes(boxes, labels, plan), plan
 
 
 def collate_targets(batch):
     """[(image, [n, 5] targets, flags or AugPlan)] -> (images, flags / plans, [M, 6] targets with the
-    batch index first)."""
+    batch index first).  A mosaic sample's entry is (image list, targets, MosaicPlan); its image list
+    stays one entry of ``images``."""
     images, flags, rows = [], [], []
     for i, (img, t, f) in enumerate(batch):
         images.append(img)
@@ -440,8 +765,15 @@ def collate_targets(batch):
 
 
 def collate_to_gpu(batch, img_size, device, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD):
-    """dataset.py collate_fn output on the GPU: ([B, 3, H, W] normalised images, [M, 6] targets)."""
+    """dataset.py collate_fn output on the GPU: ([B, 3, H, W] normalised images, [M, 6] targets).
+    A batch with at least one mosaic sample goes through mosaic_normalize whole (its plain samples
+    as degenerate records: still one launch); any other batch takes the paths it took before."""
     images, extra, targets = collate_targets(batch)
+    if any(isinstance(e, MosaicPlan) for e in extra):
+        dev_images = [to_device(im, device) if isinstance(im, (list, tuple)) else to_device([im], device)[0]
+                      for im in images]
+        x = mosaic_normalize(dev_images, extra, img_size, mean, std, dtype)
+        return x, targets.to(device, non_blocking=True)
     dev_images = to_device(images, device)
     if extra and isinstance(extra[0], AugPlan):
         x = augment_normalize(dev_images, extra, img_size, mean, std, dtype)
