@@ -285,6 +285,14 @@ yms_status yms_sppf_pool_fwd(int dtype, int n, int h, int w, int c, void* buf, i
 size_t yms_sppf_ws_bytes(int n, int h, int w, int c);
 yms_status yms_sppf_pool_bwd(int dtype, int n, int h, int w, int c, const void* buf, int ld,
                              int off, void* gbuf, int gld, int goff, void* ws, void* stream);
+/* 1 when both entry points above run the shape as one launch with the planes in LDS (16-bit
+ * dtypes, h * w within the LDS budget); every other shape runs one launch per pool (forward) or
+ * two (backward, which alone uses ws).  Same results either way. */
+int yms_sppf_fused_fits(int dtype, int h, int w, int c);
+/* Process-wide route for tests and same-tree A/Bs: 0 = always the per-pool launches, 1 = one
+ * launch where yms_sppf_fused_fits (the default); a negative v only queries.  Returns the
+ * previous value. */
+int yms_sppf_route_set(int v);
 yms_status yms_upsample2x_fwd(int dtype, int n, int h, int w, int c, const void* x, int x_ld,
                               int x_off, void* y, int y_ld, int y_off, void* stream);
 yms_status yms_upsample2x_bwd(int dtype, int n, int h, int w, int c, const void* gy, int gy_ld,

@@ -821,7 +821,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(BnGroup<PassJob
 // SPPF pools: slot k = clipped (4k+1)x(4k+1) window max of slot 0 (== k chained MaxPool5).
 // ------------------------------------------------------------------------------------------
 // One MaxPool2d(5, 1, 2) of the SPPF chain: slot `out` = pool5(slot `in`) (-inf padding).
-// The chain p1 = pool(x), p2 = pool(p1), p3 = pool(p2) runs as three launches (75 loads per
+// For the planes the one-launch kernels below do not take (yms_sppf_fused_fits: fp32, more than 585
+// positions), the chain p1 = pool(x), p2 = pool(p1), p3 = pool(p2) runs as three launches (75 loads per
 // output group instead of the 169 of a direct 13x13 window); max is exact and a NaN in the window
 // wins (torch's `val > max || isnan(val)`), so the result is bit-identical to the reference's chained
 // pools.
@@ -929,6 +930,261 @@ __global__ void pool5_gather_kernel(int n, int h, int w, int c, const uint8_t* a
       }
     }
     store8(g + (((long)b * h + y) * w + x) * ld + in_off + c0, nv, acc);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// SPPF chain in one launch (16-bit types, planes that fit the LDS budget below)
+// ------------------------------------------------------------------------------------------
+// One block owns one (image, 8-channel chunk): its h x w plane of 16-B items lives in LDS for
+// the whole chain, so the intermediate slots never come back from memory and nothing is shared
+// between blocks.  Each 5x5 pool runs as a row pass and a column pass (10 taps instead of 25).
+// That is the 25-tap scan of pool5_fwd_kernel / pool5_argmax_kernel bit for bit: every in-bounds
+// row of a clipped window has the same in-bounds columns, the row pass keeps the first maximum
+// (or the last NaN) of its row, and the column pass, replacing on `v > m || v != v` over rows in
+// order, keeps the first row holding the maximum (or the last holding a NaN) -- the lexicographic
+// (row, column) choice of the 2-D scan, zero sign and argmax included.
+//
+// Logical block l = image * G + chunk, chunks fastest, in dw_block's order (dwconv.hip): the grid
+// is padded to a multiple of 8 and block i, which runs on XCD i % 8, takes logical block
+// (i % 8) * (grid / 8) + i / 8.  The eight chunk-blocks that share a pixel's 128-B line are then
+// consecutive blocks of one XCD and find the rest of each line in its L2.
+constexpr int SPPF_NP = 3;                    // plane positions per thread (256 threads)
+constexpr int SPPF_BWD_BPP = 56;              // backward LDS bytes per position (see the kernel)
+constexpr int SPPF_LDS_MAX = 32 * 1024;       // per block: two blocks fit beside a 64-KB weight-gradient block
+
+template <typename T>
+__device__ __forceinline__ u32x4 sppf_pack(const float (&v)[8]) {
+  T t[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) t[i] = (T)v[i];
+  u32x4 r;
+  __builtin_memcpy(&r, t, sizeof(r));
+  return r;
+}
+template <typename T>
+__device__ __forceinline__ void sppf_unpack(const u32x4& r, float (&v)[8]) {
+  Raw8<T> q;
+  q.v[0] = r;
+  unpack8<T>(q, v);
+}
+__device__ __forceinline__ bool sppf_block(int nlog, int G, int& b, int& g) {
+  const int l = (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  if (l >= nlog) return false;
+  g = l % G;
+  b = l / G;
+  return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sppf_chain_fwd_kernel(int nlog, int h, int w, int c, T* buf, int ld, int off) {
+  static_assert(sizeof(T) == 2, "16-bit planes");
+  extern __shared__ u32x4 sppf_lds[];
+  int b, g;
+  if (!sppf_block(nlog, c >> 3, b, g)) return;
+  const int P = h * w;
+  u32x4* X = sppf_lds;        // slot k - 1, then slot k
+  u32x4* R = sppf_lds + P;    // row maxima
+  T* base = buf + (long)b * P * ld + off + g * 8;
+  int py[SPPF_NP], px[SPPF_NP];
+#pragma unroll
+  for (int i = 0; i < SPPF_NP; ++i) {
+    const int p = threadIdx.x + 256 * i;
+    py[i] = p / w;
+    px[i] = p - py[i] * w;
+    if (p < P) X[p] = *reinterpret_cast<const u32x4*>(base + (long)p * ld);
+  }
+  __syncthreads();
+  for (int k = 1; k <= 3; ++k) {
+#pragma unroll
+    for (int i = 0; i < SPPF_NP; ++i) {
+      const int p = threadIdx.x + 256 * i;
+      if (p >= P) continue;
+      float m[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
+      const int x0 = max(px[i] - 2, 0), x1 = min(px[i] + 2, w - 1);
+      for (int q = p - px[i] + x0; q <= p - px[i] + x1; ++q) {
+        float v[8];
+        sppf_unpack<T>(X[q], v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) m[j] = (v[j] > m[j] || v[j] != v[j]) ? v[j] : m[j];
+      }
+      R[p] = sppf_pack<T>(m);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < SPPF_NP; ++i) {
+      const int p = threadIdx.x + 256 * i;
+      if (p >= P) continue;
+      float m[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
+      const int y0 = max(py[i] - 2, 0), y1 = min(py[i] + 2, h - 1);
+      for (int yy = y0; yy <= y1; ++yy) {
+        float v[8];
+        sppf_unpack<T>(R[yy * w + px[i]], v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) m[j] = (v[j] > m[j] || v[j] != v[j]) ? v[j] : m[j];
+      }
+      const u32x4 r = sppf_pack<T>(m);
+      X[p] = r;     // the row pass was the last reader of slot k - 1
+      *reinterpret_cast<u32x4*>(base + (long)p * ld + k * c) = r;
+    }
+    __syncthreads();
+  }
+}
+
+// Backward of the chain.  LDS per position: V (16 B: the value plane of slot k - 1; once the row
+// pass has read it, its first 8 B per position hold the argmax bytes), two 16-B planes that
+// alternate between "gradient of slot k" and "row maxima, then the rounded gradient of slot
+// k - 1", and 8 B of row argmax columns: 56 B.  The next stage's value plane and the gradient
+// its positions start from (slot k - 2) wait in registers, loaded before the gather that hides them.
+template <typename T>
+__global__ __launch_bounds__(256) void sppf_chain_bwd_kernel(int nlog, int h, int w, int c, const T* buf, int ld,
+                                                             int off, T* gbuf, int gld, int goff) {
+  static_assert(sizeof(T) == 2, "16-bit planes");
+  extern __shared__ u32x4 sppf_lds[];
+  int b, g;
+  if (!sppf_block(nlog, c >> 3, b, g)) return;
+  const int P = h * w;
+  u32x4* V = sppf_lds;
+  uint2* A = reinterpret_cast<uint2*>(sppf_lds);
+  u32x4* GI = sppf_lds + P;          // gradient of slot k
+  u32x4* GO = sppf_lds + 2 * P;      // row maxima, then gradient of slot k - 1
+  uint2* RK = reinterpret_cast<uint2*>(sppf_lds + 3 * P);
+  const T* vbase = buf + (long)b * P * ld + off + g * 8;
+  T* gbase = gbuf + (long)b * P * gld + goff + g * 8;
+  u32x4 vreg[SPPF_NP], greg[SPPF_NP];
+#pragma unroll
+  for (int i = 0; i < SPPF_NP; ++i) {
+    const int p = threadIdx.x + 256 * i;
+    vreg[i] = greg[i] = u32x4{0u, 0u, 0u, 0u};
+    if (p < P) {
+      vreg[i] = *reinterpret_cast<const u32x4*>(vbase + (long)p * ld + 2 * c);
+      greg[i] = *reinterpret_cast<const u32x4*>(gbase + (long)p * gld + 2 * c);
+      GI[p] = *reinterpret_cast<const u32x4*>(gbase + (long)p * gld + 3 * c);
+    }
+  }
+  for (int k = 3; k >= 1; --k) {
+#pragma unroll
+    for (int i = 0; i < SPPF_NP; ++i) {
+      const int p = threadIdx.x + 256 * i;
+      if (p < P) V[p] = vreg[i];     // the previous gather's reads of A ended at its closing barrier
+    }
+    __syncthreads();
+    // row pass: first maximum (last NaN) of the in-bounds columns of each row window, and its kx
+#pragma unroll 1
+    for (int p = threadIdx.x; p < P; p += 256) {
+      const int px = p % w;
+      const int kx0 = max(2 - px, 0), kx1 = min(w + 1 - px, 4);
+      float best[8];
+      uint32_t idx[8];
+      sppf_unpack<T>(V[p - 2 + kx0], best);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) idx[j] = (uint32_t)kx0;
+      for (int kx = kx0 + 1; kx <= kx1; ++kx) {
+        float v[8];
+        sppf_unpack<T>(V[p - 2 + kx], v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const bool t = v[j] > best[j] || v[j] != v[j];
+          best[j] = t ? v[j] : best[j];
+          idx[j] = t ? (uint32_t)kx : idx[j];
+        }
+      }
+      GO[p] = sppf_pack<T>(best);
+      RK[p] = make_uint2(idx[0] | idx[1] << 8 | idx[2] << 16 | idx[3] << 24,
+                         idx[4] | idx[5] << 8 | idx[6] << 16 | idx[7] << 24);
+    }
+    __syncthreads();
+    // column pass over the row results: the window's argmax byte ky * 5 + kx
+#pragma unroll 1
+    for (int p = threadIdx.x; p < P; p += 256) {
+      const int py = p / w;
+      const int ky0 = max(2 - py, 0), ky1 = min(h + 1 - py, 4);
+      float best[8];
+      uint32_t idx[8];     // the word of candidate bytes that holds channel j's
+      {
+        const int q = p + (ky0 - 2) * w;
+        sppf_unpack<T>(GO[q], best);
+        const uint2 rk = RK[q];
+        const uint32_t a = 5u * ky0 * 0x01010101u;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) idx[j] = (j < 4 ? rk.x : rk.y) + a;
+      }
+      for (int ky = ky0 + 1; ky <= ky1; ++ky) {
+        const int q = p + (ky - 2) * w;
+        float v[8];
+        sppf_unpack<T>(GO[q], v);
+        const uint2 rk = RK[q];
+        const uint32_t a = 5u * ky * 0x01010101u;
+        const uint32_t cx = rk.x + a, cy = rk.y + a;     // bytes < 25: no carry between them
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const bool t = v[j] > best[j] || v[j] != v[j];
+          best[j] = t ? v[j] : best[j];
+          idx[j] = t ? (j < 4 ? cx : cy) : idx[j];
+        }
+      }
+      uint2 a = make_uint2(0u, 0u);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        a.x |= idx[j] & (0xffu << (8 * j));
+        a.y |= idx[4 + j] & (0xffu << (8 * j));
+      }
+      A[p] = a;      // V's space: the row pass was its last reader
+    }
+    __syncthreads();
+    // the gradient each position starts from takes the row maxima's place (read no more); then the
+    // next stage's value plane and starting gradient go in flight over the gather
+#pragma unroll
+    for (int i = 0; i < SPPF_NP; ++i) {
+      const int p = threadIdx.x + 256 * i;
+      if (p < P) GO[p] = greg[i];
+    }
+    if (k > 1) {
+#pragma unroll
+      for (int i = 0; i < SPPF_NP; ++i) {
+        const int p = threadIdx.x + 256 * i;
+        if (p < P) {
+          vreg[i] = *reinterpret_cast<const u32x4*>(vbase + (long)p * ld + (k - 2) * c);
+          greg[i] = *reinterpret_cast<const u32x4*>(gbase + (long)p * gld + (k - 2) * c);
+        }
+      }
+    }
+    // gather: g[slot k - 1] + the gradients of the outputs whose argmax is this position, in
+    // pool5_gather_kernel's (ky, kx) order, fp32, rounded once
+#pragma unroll 1
+    for (int p = threadIdx.x; p < P; p += 256) {
+      const int py = p / w, px = p - py * w;
+      float acc[8];
+      sppf_unpack<T>(GO[p], acc);     // this thread's own write
+      // output (y - ky + 2, x - kx + 2) sees this input at window offset (ky, kx)
+      const int ky0 = max(py + 3 - h, 0), ky1 = min(py + 2, 4);
+      const int kx0 = max(px + 3 - w, 0), kx1 = min(px + 2, 4);
+      for (int ky = ky0; ky <= ky1; ++ky) {
+        for (int kx = kx0; kx <= kx1; ++kx) {
+          const int o = p + (2 - ky) * w + 2 - kx;
+          const uint2 av = A[o];
+          float gv[8];
+          sppf_unpack<T>(GI[o], gv);
+          const uint32_t want = (uint32_t)(ky * 5 + kx);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const uint32_t aj = ((j < 4 ? av.x : av.y) >> (8 * (j & 3))) & 0xffu;
+            if (aj == want) acc[j] += gv[j];
+          }
+        }
+      }
+      const u32x4 r = sppf_pack<T>(acc);
+      *reinterpret_cast<u32x4*>(gbase + (long)p * gld + (k - 1) * c) = r;
+      GO[p] = r;     // the next stage's incoming gradient
+    }
+    __syncthreads();
+    u32x4* t = GI;
+    GI = GO;
+    GO = t;
   }
 }
 
@@ -1471,11 +1727,41 @@ size_t yms_sppf_ws_bytes(int n, int h, int w, int c) {
   return (size_t)n * h * w * ((c + 7) / 8) * 8;
 }
 
+// The one-launch chain takes 16-bit planes whose backward fits SPPF_LDS_MAX (h * w <= 585); every
+// other shape runs the three-launch kernels.
+int yms_sppf_fused_fits(int dtype, int h, int w, int c) {
+  if (dtype != YMS_BF16 && dtype != YMS_F16) return 0;
+  if (h <= 0 || w <= 0 || c <= 0 || c % 8 != 0) return 0;
+  const long p = (long)h * w;
+  return p * SPPF_BWD_BPP <= SPPF_LDS_MAX && p <= 256 * SPPF_NP;
+}
+static int& sppf_route() {
+  static int r = 1;
+  return r;
+}
+int yms_sppf_route_set(int v) {
+  const int prev = sppf_route();
+  if (v >= 0) sppf_route() = v ? 1 : 0;
+  return prev;
+}
+
 yms_status yms_sppf_pool_fwd(int dtype, int n, int h, int w, int c, void* buf, int ld, int off,
                              void* stream) {
   if (n <= 0 || h <= 0 || w <= 0 || !buf || !vok(ld, off, 4 * c) || c % 8 != 0) return YMS_ERR_INVALID;
   const long items = (long)n * h * w * ((c + 7) / 8);
   if (items >= (1l << 31)) return YMS_ERR_UNSUPPORTED;
+  if (sppf_route() && yms_sppf_fused_fits(dtype, h, w, c)) {
+    const int nlog = n * (c / 8);
+    const dim3 grid((unsigned)rup(nlog, 8));
+    const size_t lds = (size_t)h * w * 32;
+    if (dtype == YMS_BF16)
+      hipLaunchKernelGGL(sppf_chain_fwd_kernel<bf16>, grid, dim3(256), lds, (hipStream_t)stream, nlog, h, w, c,
+                         (bf16*)buf, ld, off);
+    else
+      hipLaunchKernelGGL(sppf_chain_fwd_kernel<f16>, grid, dim3(256), lds, (hipStream_t)stream, nlog, h, w, c,
+                         (f16*)buf, ld, off);
+    return launch_status();
+  }
   for (int k = 1; k <= 3; ++k)
     YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL(pool5_fwd_kernel<T>, dim3(grid_for(items)), dim3(256), 0,
                                                  (hipStream_t)stream, n, h, w, c, (T*)buf, ld,
@@ -1491,9 +1777,25 @@ yms_status yms_sppf_pool_bwd(int dtype, int n, int h, int w, int c, const void* 
   const long items = (long)n * h * w * ((c + 7) / 8);
   if (items >= (1l << 31)) return YMS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  // (round 3: a bit-identical whole-map fused backward, one launch per pool with the argmax and the
-  // gather in LDS, was slower inside the overlapped step -- 18.37-18.47 -> 18.51-18.57 ms,
-  // profiles/r03v_sppf_fused_ab.txt: its 64 KB-LDS blocks waited for the side stream's LDS)
+  // One launch for the three pools (sppf_chain_bwd_kernel) where the plane fits: 22 KB of LDS per
+  // block at 20x20, so its blocks sit beside the side stream's weight gradients (the round-3 attempt,
+  // one 64-KB-LDS launch per pool, lost 0.1 ms in the step waiting for that LDS,
+  // profiles/r03v_sppf_fused_ab.txt).  In the step the chain's kernels take 424 -> 162 us and the
+  // step 16.90 -> 16.64 ms (profiles/sppf_chain_stats_*.txt, sppf_chain_ab.txt).  The fused backward
+  // is VALU-bound (94 % of the SIMDs' issue cycles, profiles/sppf_chain_micro.txt): the 25-tap
+  // gather's compare / select / add per channel is what is left, not memory.
+  if (sppf_route() && yms_sppf_fused_fits(dtype, h, w, c)) {
+    const int nlog = n * (c / 8);
+    const dim3 grid((unsigned)rup(nlog, 8));
+    const size_t lds = (size_t)h * w * SPPF_BWD_BPP;
+    if (dtype == YMS_BF16)
+      hipLaunchKernelGGL(sppf_chain_bwd_kernel<bf16>, grid, dim3(256), lds, st, nlog, h, w, c, (const bf16*)buf, ld,
+                         off, (bf16*)gbuf, gld, goff);
+    else
+      hipLaunchKernelGGL(sppf_chain_bwd_kernel<f16>, grid, dim3(256), lds, st, nlog, h, w, c, (const f16*)buf, ld,
+                         off, (f16*)gbuf, gld, goff);
+    return launch_status();
+  }
   for (int k = 3; k >= 1; --k) {
     // pool k reads slot k-1 (value buf) and produced slot k; push grad of slot k into slot k-1
     YMS_DT_DISPATCH(dtype, T, {

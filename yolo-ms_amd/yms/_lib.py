@@ -132,6 +132,8 @@ _SIGS = {
     "yms_sppf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "yms_sppf_pool_fwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "yms_sppf_pool_bwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
+    "yms_sppf_fused_fits": (_I, [_I, _I, _I, _I]),
+    "yms_sppf_route_set": (_I, [_I]),
     "yms_upsample2x_fwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P]),
     "yms_upsample2x_bwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P]),
     "yms_pack_input": (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P]),
