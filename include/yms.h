@@ -27,6 +27,8 @@
  *   yms_augment_normalize
  *   yms_mosaic_normalize    the config's `mosaic` / `mixup` keys, which dataset.py never reads:
  *                           YOLOv5 load_mosaic / random_perspective / mixup semantics, opt-in
+ *   yms_optim_*             tools/utils.py:11-25 get_optimizer's torch.optim.SGD / Adam step, plus the
+ *                           weight EMA, clip_grad_norm_ and non-finite guard (train.py:365,376), opt-in
  */
 #ifndef YMS_H
 #define YMS_H
@@ -458,6 +460,88 @@ yms_status yms_nms_classwise(int n, int A, int nc, const float* boxes_xyxy, cons
 /* Plain torchvision.ops.nms(boxes[m,4], scores[m], iou) on one set -> keep[m], *count. */
 yms_status yms_nms_single(int m, const float* boxes, const float* scores, double iou,
                           int64_t* keep, int* count, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- optimizer step: SGD / Adam + weight EMA + norm clipping + non-finite skip ------------ */
+/* Replaces torch.optim.SGD / Adam behind tools/utils.py:11-25 get_optimizer, the
+ * torch.isnan(loss) + loss.item() guard of train.py:365,376, and the ModelEMA / clip_grad_norm_
+ * every YOLOv8 recipe adds, in a launch count that does not depend on the number of tensors: the
+ * tensors are described by a device table of fixed-size chunks instead of kernel arguments.
+ *
+ * A job is one fp32 tensor of `count` >= 1 elements.  param: its device address (16-B alignment is
+ * used when present, 4-B is enough).  grad: the gradient as a byte offset from the grad_base given
+ * per call (the flat gradient arena), or an absolute address (YMS_OPTIM_GRAD_ABS), or none
+ * (YMS_OPTIM_GRAD_NONE: no update; the EMA, if any, still follows the tensor).  state0 / state1 / ema:
+ * ELEMENT offsets of the job's slots in the three flat fp32 buffers given to
+ * yms_optim_table_build (momentum | exp_avg, exp_avg_sq, EMA), -1 = no slot.  An update needs
+ * state0 (and state1 for Adam); YMS_OPTIM_EMA needs ema >= 0.  group: index into the hyper array. */
+#define YMS_OPTIM_SGD 0
+#define YMS_OPTIM_ADAM 1
+#define YMS_OPTIM_GRAD_NONE 1
+#define YMS_OPTIM_GRAD_ABS 2
+#define YMS_OPTIM_EMA 4
+#define YMS_OPTIM_MAX_GROUPS 8
+typedef struct {
+  void* param;
+  int64_t grad;
+  int64_t state0, state1, ema;
+  int64_t count;
+  int group, flags;
+} yms_optim_job;
+/* One row of the device table: at most yms_optim_chunk_elems() consecutive elements of ONE job, so a
+ * block's work does not depend on which tensor it lands in.  All addresses are absolute but g,
+ * which keeps the job's meaning (offset of the chunk's first gradient element, or its address). */
+typedef struct {
+  float* p;
+  int64_t g;
+  float* s0;
+  float* s1;
+  float* e;
+  int n;
+  short group, flags;
+} yms_optim_chunk;
+/* Device arrays the step reads (never kernel arguments, so a captured graph sees a new value):
+ * max_norm <= 0 = no clipping; skip_nonfinite != 0 = write nothing when the norm is not finite;
+ * ema_decay / ema_tau: delta = decay * (1 - exp(-k / tau)), tau <= 0 = the plain decay;
+ * group[i] = { lr, momentum | beta1, beta2, eps, weight_decay, nesterov != 0, 0, 0 }.  Doubles, as
+ * torch holds them: 1 - beta2 taken from a float 0.999 is already off in the fifth digit. */
+typedef struct {
+  double max_norm, skip_nonfinite, ema_decay, ema_tau;
+  double group[YMS_OPTIM_MAX_GROUPS][8];
+} yms_optim_hyper;
+typedef struct {
+  int step, ema_step, skipped;   /* updates applied, EMA updates applied, steps skipped */
+  float grad_norm;               /* the last step's gradient norm (with partials) */
+} yms_optim_counters;
+/* HOST only (no launch): elements per chunk; rows / bytes of the table of a job list (-1 / 0: invalid
+ * jobs); the table itself into caller-owned HOST memory (the caller uploads it; it holds no gradient
+ * address in the offset form, so one table serves every arena and is valid inside a captured
+ * graph); and the number of partial sums yms_optim_grad_norm writes for a table of nchunks rows. */
+int yms_optim_chunk_elems(void);
+long yms_optim_table_chunks(int njobs, const yms_optim_job* jobs);
+size_t yms_optim_table_bytes(int njobs, const yms_optim_job* jobs);
+yms_status yms_optim_table_build(int njobs, const yms_optim_job* jobs, float* state0, float* state1, float* ema,
+                                 void* table, size_t table_bytes);
+int yms_optim_norm_partials(long nchunks);
+/* partials[yms_optim_norm_partials(nchunks)] <- sums of squares of the table's gradients: one
+ * launch, no atomics, a fixed summation tree (bit-reproducible; no chain of more than 128 sequential
+ * fp32 additions). */
+yms_status yms_optim_grad_norm(const void* table, long nchunks, const void* grad_base, float* partials,
+                               void* stream);
+/* One optimizer step in two launches (the update over the table, then a one-block tick that advances
+ * the counters and stores the norm).  fp32 arithmetic as torch.optim; the bias corrections and the
+ * EMA factor in fp64 from the device counters:
+ *   SGD   d = g + wd p;  b' = d (first update) | mom b + d;  p' = p - lr (nesterov ? d + mom b' : b')
+ *   Adam  d = g + wd p;  m' = b1 m + (1-b1) d;  v' = b2 v + (1-b2) d^2;
+ *         p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps),  bc_i = 1 - b_i^t   (no amsgrad, not AdamW)
+ *   EMA   e' = delta e + (1 - delta) p'
+ * partials != NULL (npartials of yms_optim_grad_norm's sums): every block re-reduces them in one
+ * fixed order, scales g by min(1, max_norm / (norm + 1e-6)) (torch's clip_grad_norm_) and, when the
+ * norm is not finite and skip_nonfinite is set, writes nothing (the tick then counts a skipped step). */
+yms_status yms_optim_step(int kind, const void* table, long nchunks, const void* grad_base,
+                          const yms_optim_hyper* hyper, yms_optim_counters* counters, const float* partials,
+                          int npartials, void* stream);
+/* Exchange every YMS_OPTIM_EMA row's tensor with its EMA slot, in place, in one launch. */
+yms_status yms_optim_swap(const void* table, long nchunks, void* stream);
 
 #ifdef __cplusplus
 }

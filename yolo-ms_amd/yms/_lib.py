@@ -79,6 +79,28 @@ class BnBwdFinalizeJob(ctypes.Structure):
     _fields_ = _fields("c:i ws:p rows:i count:l dgamma:p dbeta:p coef:p")
 
 
+# optimizer records (include/yms.h, "optimizer step")
+OPTIM_SGD, OPTIM_ADAM = 0, 1
+OPTIM_GRAD_NONE, OPTIM_GRAD_ABS, OPTIM_EMA = 1, 2, 4
+OPTIM_MAX_GROUPS = 8
+
+
+class OptimJob(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p)] + [(k, ctypes.c_int64) for k in
+                                                ("grad", "state0", "state1", "ema", "count")] + [
+        ("group", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+class OptimChunk(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_int64), ("s0", ctypes.c_void_p), ("s1", ctypes.c_void_p),
+                ("e", ctypes.c_void_p), ("n", ctypes.c_int), ("group", ctypes.c_short), ("flags", ctypes.c_short)]
+
+
+class OptimHyper(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("max_norm", "skip_nonfinite", "ema_decay", "ema_tau")] + [
+        ("group", ctypes.c_double * 8 * OPTIM_MAX_GROUPS)]
+
+
 _L = ctypes.c_long
 _F = ctypes.c_float
 _D = ctypes.c_double
@@ -169,6 +191,14 @@ _SIGS = {
     "yms_nms_ws_bytes_min": (_SZ, [_I, _I, _I]),
     "yms_nms_classwise": (_I, [_I, _I, _I, _P, _P, _P, _D, _P, _P, _P, _P, _SZ, _P]),
     "yms_nms_single": (_I, [_I, _P, _P, _D, _P, _P, _P, _SZ, _P]),
+    "yms_optim_chunk_elems": (_I, []),
+    "yms_optim_table_chunks": (_L, [_I, _P]),
+    "yms_optim_table_bytes": (_SZ, [_I, _P]),
+    "yms_optim_table_build": (_I, [_I, _P, _P, _P, _P, _P, _SZ]),
+    "yms_optim_norm_partials": (_I, [_L]),
+    "yms_optim_grad_norm": (_I, [_P, _L, _P, _P, _P]),
+    "yms_optim_step": (_I, [_I, _P, _L, _P, _P, _P, _P, _I, _P]),
+    "yms_optim_swap": (_I, [_P, _L, _P]),
 }
 
 EXPORTED = tuple(_SIGS)
