@@ -1335,7 +1335,8 @@ static bool dw_shape_ok(const yms_dw_shape* s) {
   return s && s->n > 0 && s->h > 0 && s->w > 0 && s->c > 0 && s->c % 8 == 0 && (s->k == 3 || s->k == 5 || s->k == 7 || s->k == 9) &&
          s->dtype >= 0 && s->dtype <= 2 && (long)s->n * s->h * s->w < (1l << 31);
 }
-static bool dw_view_ok(int ld, int off, int c) { return ld % 8 == 0 && off % 8 == 0 && off + c <= ld; }
+static bool dw_view_ok(int ld, int off, int c) { return ld % 8 == 0 && off >= 0 && off % 8 == 0 && off + c <= ld; }
+static bool dw_dtype_ok(int dtype) { return dtype == YMS_F32 || dtype == YMS_BF16 || dtype == YMS_F16; }
 // forward / dgrad read one image through a raw buffer resource: 32-bit byte offsets below the
 // out-of-range marker NT_OOB
 static bool dw_image_fits(const yms_dw_shape* s, int ld) {
@@ -1689,7 +1690,8 @@ yms_status yms_dwconv_wgrad(const yms_dw_shape* s, const void* x, int x_ld, int 
 
 yms_status yms_add_views(int dtype, long npix, int c, const void* a, int a_ld, int a_off, const void* b, int b_ld,
                          int b_off, void* y, int y_ld, int y_off, int accumulate, void* stream) {
-  if (npix <= 0 || c <= 0 || c % 8 || !a || !y || !dw_view_ok(a_ld, a_off, c) || !dw_view_ok(y_ld, y_off, c))
+  if (!dw_dtype_ok(dtype) || npix <= 0 || c <= 0 || c % 8 || !a || !y || !dw_view_ok(a_ld, a_off, c) ||
+      !dw_view_ok(y_ld, y_off, c))
     return YMS_ERR_INVALID;
   if (b && !dw_view_ok(b_ld, b_off, c)) return YMS_ERR_INVALID;
   const long items = npix * (c / 8);
@@ -1701,8 +1703,8 @@ yms_status yms_add_views(int dtype, long npix, int c, const void* a, int a_ld, i
 
 yms_status yms_add_grad2(int dtype, long npix, int c, const void* g, int g_ld, int g_off, void* y1, int ld1,
                          int off1, int acc1, void* y2, int ld2, int off2, int acc2, void* stream) {
-  if (npix <= 0 || c <= 0 || c % 8 || !g || !y1 || !y2 || !dw_view_ok(g_ld, g_off, c) || !dw_view_ok(ld1, off1, c) ||
-      !dw_view_ok(ld2, off2, c))
+  if (!dw_dtype_ok(dtype) || npix <= 0 || c <= 0 || c % 8 || !g || !y1 || !y2 || !dw_view_ok(g_ld, g_off, c) ||
+      !dw_view_ok(ld1, off1, c) || !dw_view_ok(ld2, off2, c))
     return YMS_ERR_INVALID;
   const long items = npix * (c / 8);
   YMS_DW_T(dtype, hipLaunchKernelGGL((add_grad2_kernel<TT>), dim3(add_grid(items)), dim3(256), 0, (hipStream_t)stream,
