@@ -13,11 +13,16 @@ def r8(c):
     return (c + 7) // 8 * 8
 
 
-def nhwc(x, dtype, ld=None, off=0):
-    """NCHW fp32 -> zero-padded NHWC [n,h,w,ld] buffer of dtype with x at channel offset off."""
+def nhwc(x, dtype, ld=None, off=0, fill=0.0):
+    """NCHW fp32 -> zero-padded NHWC [n,h,w,ld] buffer of dtype with x at channel offset off.  fill: the
+    value of the channels outside [off, off + r8(c)), the neighbouring slots of a wider buffer (x's own
+    padding up to r8(c) stays zero, as the producers keep it)."""
     n, c, h, w = x.shape
     ld = ld or r8(off + c)
     buf = torch.zeros((n, h, w, ld), dtype=dtype, device="cuda")
+    if fill != 0.0:                      # (NaN included)
+        buf[..., :off] = fill
+        buf[..., off + r8(c):] = fill
     buf[..., off:off + c] = x.permute(0, 2, 3, 1).to(dtype)
     return buf
 

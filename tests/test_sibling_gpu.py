@@ -62,7 +62,9 @@ def test_sibling_head_convs_match_unfused(version, nc, size, monkeypatch):
     for k in b0:
         assert torch.equal(b1[k], b0[k]), k
     # (nc = 3: the z buffers' padding channels start zeroed -- arena garbage there used to turn the
-    # input gradient NaN through zero weight rows, fused or not)
+    # input gradient NaN through zero weight rows, fused or not.  A fresh arena is usually zero pages,
+    # so this only watches for it: tests/test_arena_poison_gpu.py fills the arenas with NaN and
+    # test_gate_reports_unzeroed_z_padding there takes exactly this zeroing away)
     for gg in (g1, g0):
         bad = [k for k, t in gg.items() if not torch.isfinite(t).all()]
         assert not bad, bad[:5]
@@ -156,7 +158,8 @@ def test_sibling_fallback_with_frozen_members(pattern, nc, monkeypatch):
 @pytest.mark.parametrize("nc", [1, 17])
 def test_sibling_bf16_grads_finite_ragged_nc(nc, monkeypatch):
     """The z buffers' padding channels (65 -> 72, 81 -> 88) start zeroed: arena garbage there used to
-    turn the input gradient NaN through zero weight rows (asserted for nc = 3 above)."""
+    turn the input gradient NaN through zero weight rows (asserted for nc = 3 above).  The deterministic
+    check, on arenas filled with NaN, is tests/test_arena_poison_gpu.py (nc = 3 and 17)."""
     torch.manual_seed(0)
     sd = YOLOv8("n", nc).state_dict()
     x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(1)).cuda()
