@@ -432,6 +432,22 @@ yms_status yms_det_loss(int dtype, int batch, int nc, int nlevels, const void* c
 yms_status yms_scale_by_device_scalar(int dtype, int nbuf, void* const* bufs, const long* counts, const float* g,
                                       void* stream);
 
+/* ---- task-aligned assigner loss (opt-in; DESIGN.md "Task-aligned loss") --------------------- */
+/* YOLOv8's published v8DetectionLoss + TaskAlignedAssigner, restated in tests/tal_ref.py (the
+ * definition; parity with the ultralytics package is not pinned).  Arguments as yms_det_loss without
+ * iou_type / pos_weight (CIoU, BCE weight 1).  A target row whose image is outside [0, batch) or
+ * whose class is outside [0, nc) is ignored.  topk 1..10; alpha, beta >= 0: the exponents of the
+ * alignment metric sigmoid(class logit)^alpha * max(CIoU, 0)^beta (published 10, 0.5, 6.0).
+ * out (device fp32 [4]) = total, box, cls, dfl with total = batch * (lambdas . terms); grads =
+ * d(total)/d(maps).  assign_gt / assign_score: NULL or device [batch * anchors] diagnostics, the
+ * target row each anchor is assigned to (-1: background) and its target score. */
+size_t yms_tal_loss_ws_bytes(int batch, int anchors, int nc, int n_targets);
+yms_status yms_tal_loss(int dtype, int batch, int nc, int nlevels, const void* const* maps, void* const* grads,
+                        const int* hs, const int* ws_, const float* strides, int ld, const float* targets,
+                        int n_targets, float img_w, float img_h, int topk, float alpha, float beta,
+                        const float* lambdas, void* ws, size_t ws_bytes, float* out, int* assign_gt,
+                        float* assign_score, void* stream);
+
 /* ---- head decode + NMS ------------------------------------------------------------------- */
 /* Raw head maps lvl[i]: NHWC [n, h_i, w_i, no_ld] with channels (64 DFL box logits, nc cls
  * logits).  out: [n, A, 4+nc] fp32 = (cx, cy, w, h)*stride_i, sigmoid(cls).  When nms_score

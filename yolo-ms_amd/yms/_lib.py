@@ -184,6 +184,9 @@ _SIGS = {
     "yms_mosaic_normalize": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "yms_det_loss": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _P, _P, _P, _SZ, _P, _P]),
     "yms_scale_by_device_scalar": (_I, [_I, _I, _P, _P, _P, _P]),
+    "yms_tal_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "yms_tal_loss": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _P, _P, _SZ, _P, _P, _P,
+                          _P]),
     "yms_head_decode": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P]),
     "yms_dfl": (_I, [_I, _I, _I, _I, _P, _P, _P]),
     "yms_nms_prep": (_I, [_I, _I, _I, _P, _F, _P, _P, _P, _P]),
