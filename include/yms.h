@@ -23,6 +23,9 @@
  *   yms_head_decode         yolov8_head.py:127-158 make_anchors + DFL (components.py:162-191)
  *   yms_nms_*               train.py:63-113 / tools/test.py:166-218 post-process and the
  *                           torchvision.ops.nms(boxes, scores, iou) call at train.py:93
+ *   yms_det_*               nothing in the reference: the COCO evaluation protocol (multi-label
+ *                           candidates, max_nms / max_det caps, letterbox unmap) around
+ *                           yms_nms_classwise, opt-in
  *   yms_resize_normalize,   tools/dataset.py:84-134 transform list + collate_fn's stack (:260)
  *   yms_augment_normalize
  *   yms_mosaic_normalize    the config's `mosaic` / `mixup` keys, which dataset.py never reads:
@@ -476,6 +479,43 @@ yms_status yms_nms_classwise(int n, int A, int nc, const float* boxes_xyxy, cons
 /* Plain torchvision.ops.nms(boxes[m,4], scores[m], iou) on one set -> keep[m], *count. */
 yms_status yms_nms_single(int m, const float* boxes, const float* scores, double iou,
                           int64_t* keep, int* count, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- COCO-protocol detect: candidates in front of yms_nms_classwise, finalize behind it --- */
+/* The protocol of the published YOLOv8 / YOLO-MS AP (ultralytics non_max_suppression): every
+ * (anchor, class) pair above conf, at most K = max_nms of them by score, NMS, at most max_det
+ * detections by score, boxes mapped back through the letterbox and clipped.  The tie rules below
+ * are this package's (ultralytics leaves ties to its sort: parity UNPINNED).
+ *
+ * yms_det_candidates: pred [n, A, 4+nc] fp32 (yms_head_decode's out).  multi_label != 0: every pair
+ * (a, c) with score > conf (NaN never, +inf does); else per anchor the pair yms_nms_prep picks (max
+ * score, ties to the lower class) when its score > conf.  class_mask: NULL or device uint8[nc], 0 =
+ * the class is dropped (after the arg-max in best-class mode).  Of an image's candidates the first K
+ * by (score descending, anchor ascending, class ascending) survive (a radix select over the score
+ * bits; ties at the threshold admitted lowest a * nc + c first) and are stored as rows in ascending
+ * a * nc + c: cand_boxes [n][K][4] xyxy (bit-equal to yms_nms_prep's), cand_score, cand_label,
+ * cand_anchor [n][K]; unused rows are zero with label and anchor -1.  cand_count[n] = min(count, K),
+ * cand_total[n] = the uncapped count.  Bit-exact and independent of block scheduling (integer
+ * atomics only); a fixed number of launches, no host read, no allocation: capture-safe.
+ * conf >= 0 (negative or NaN: YMS_ERR_INVALID), 1 <= K <= 65536, nc <= 1024, ws of
+ * yms_det_ws_bytes() bytes (the NMS workspace is not included), cand_boxes 16-byte aligned.
+ * The rows feed yms_nms_classwise(n, K, nc, cand_boxes, cand_score, cand_label, ...) as they are;
+ * class-agnostic NMS passes label 0 for every live row with nc = 1 and keeps cand_label aside.
+ *
+ * yms_det_finalize: of image b's counts[b] kept rows keep_idx[n][K] (yms_nms_classwise's output) the
+ * first max_det by (score descending, row ascending) -> det [n][max_det][6] = (x1, y1, x2, y2,
+ * score, label from true_label), det_anchor [n][max_det], det_count[n]; rows beyond the count are
+ * zero with label and anchor -1.  frames: NULL (boxes pass through) or device fp32 [n][6] =
+ * (gain_x, gain_y, pad_x, pad_y, w0, h0): each coordinate becomes min(max((v - pad) / gain, 0), w0
+ * or h0), the subtraction and the division separately rounded.  1 <= max_det <= 1024. */
+size_t yms_det_ws_bytes(int n, int A, int nc, int K);
+yms_status yms_det_candidates(int n, int A, int nc, const float* pred, float conf, int multi_label,
+                              const uint8_t* class_mask, int K, float* cand_boxes, float* cand_score,
+                              int* cand_label, int* cand_anchor, int* cand_count, int* cand_total, void* ws,
+                              size_t ws_bytes, void* stream);
+yms_status yms_det_finalize(int n, int K, int max_det, const float* cand_boxes, const float* cand_score,
+                            const int* true_label, const int* cand_anchor, const int64_t* keep_idx,
+                            const int* counts, const float* frames, float* det, int* det_anchor, int* det_count,
+                            void* stream);
 
 /* ---- optimizer step: SGD / Adam + weight EMA + norm clipping + non-finite skip ------------ */
 /* Replaces torch.optim.SGD / Adam behind tools/utils.py:11-25 get_optimizer, the

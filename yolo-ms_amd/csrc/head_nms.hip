@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "nms_pick.hpp"
 #include "yms_common.hpp"
 
 #pragma clang fp contract(off)
@@ -124,35 +125,15 @@ __global__ __launch_bounds__(256) void nms_prep_kernel(int n, int A, int nc, con
   const long stride = (long)gridDim.x * (blockDim.x >> 4);
   for (long t = blockIdx.x * (long)(blockDim.x >> 4) + (threadIdx.x >> 4); t < total; t += stride) {
     const float* q = pred + t * (4 + nc);
-    float best = -INFINITY;
-    int bl = 0x7fffffff;
-    bool any = false;
-    // this lane's classes c = sub, sub + 16, ...: loads batched 8 deep (nc = 80: one batch)
-    for (int c0 = sub; c0 < nc; c0 += 128) {
-      float v8[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int c = c0 + 16 * u;
-        v8[u] = c < nc ? q[4 + c] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int c = c0 + 16 * u;
-        if (c < nc && (!any || v8[u] > best)) { best = v8[u]; bl = c; any = true; }
-      }
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      const float ob = __shfl_xor(best, off, 16);
-      const int ol = __shfl_xor(bl, off, 16);
-      if (ob > best || (ob == best && ol < bl)) { best = ob; bl = ol; }
-    }
+    float best;
+    int bl;
+    nms_pick16(q, nc, sub, best, bl);      // nms_pick.hpp, shared with detect.hip's candidate stage
     if (sub == 0) {
-      const float cx = q[0], cy = q[1], w = q[2], h = q[3];
-      bxy[t * 4 + 0] = cx - w / 2;
-      bxy[t * 4 + 1] = cy - h / 2;
-      bxy[t * 4 + 2] = cx + w / 2;
-      bxy[t * 4 + 3] = cy + h / 2;
+      const float4 bx = nms_xyxy(q);
+      bxy[t * 4 + 0] = bx.x;
+      bxy[t * 4 + 1] = bx.y;
+      bxy[t * 4 + 2] = bx.z;
+      bxy[t * 4 + 3] = bx.w;
       score[t] = best;
       label[t] = best > conf ? bl : -1;
     }

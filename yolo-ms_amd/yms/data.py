@@ -29,6 +29,11 @@ Mosaic and MixUp (the config's ``mosaic`` / ``mixup`` keys, which the reference'
 never reads) are opt-in through ``COCODataset(..., mosaic=True)``: YOLOv5's semantics restated,
 sampled on the host (``sample_mosaic``, ``mosaic_boxes``) and composed on the GPU in one launch
 (``mosaic_normalize``); see the section below.
+
+Evaluation with the published AP protocol is opt-in too: ``letterbox_normalize`` (ultralytics'
+LetterBox restated, drawn by the Mosaic kernel) returns the batch and its frames, which
+``yms.ops.detect(frames=...)`` uses to map boxes back to the original images;
+``COCODataset(..., is_train=False, letterbox=True)`` + ``collate_to_gpu`` is the loader for it.
 """
 from __future__ import annotations
 
@@ -606,6 +611,71 @@ def mosaic_normalize(images, plans, size, mean=IMAGENET_MEAN, std=IMAGENET_STD, 
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# Letterbox (opt-in; the evaluation input of the published YOLOv8 / YOLO-MS AP) and its frames
+# ------------------------------------------------------------------------------------------
+# ultralytics' LetterBox with scaleup on and centred, restated (ultralytics is not installed: parity
+# UNPINNED): the image is resized by one gain r so that it fits the input, and centred on a canvas
+# of 114.  A FRAME is what maps a box in input pixels back to its original image:
+# (gain_x, gain_y, pad_x, pad_y, w0, h0), coordinate -> min(max((v - pad) / gain, 0), w0 | h0)
+# (yms.ops.detect(frames=...)).  On the GPU a letterboxed image is a one-layer, one-tile record of
+# yms_mosaic_normalize: canvas = output, no stage, the tile at (left, top) with the resize's
+# half-pixel map -- no kernel of its own.
+class Letterbox:
+    """LetterBox geometry of an h0 x w0 image in an H x W input: r = min(H / h0, W / w0), the
+    resized size nw, nh = round(w0 r), round(h0 r), and its corner left = round((W - nw) / 2 - 0.1),
+    top = round((H - nh) / 2 - 0.1) (Python's round, as ultralytics calls it)."""
+
+    def __init__(self, h0, w0, H, W):
+        self.h0, self.w0, self.H, self.W = int(h0), int(w0), int(H), int(W)
+        if min(self.h0, self.w0, self.H, self.W) < 1:
+            raise ValueError("yms: letterbox needs positive sizes")
+        self.r = min(self.H / self.h0, self.W / self.w0)
+        self.nw = min(self.W, max(1, round(self.w0 * self.r)))
+        self.nh = min(self.H, max(1, round(self.h0 * self.r)))
+        self.left = max(0, round((self.W - self.nw) / 2 - 0.1))
+        self.top = max(0, round((self.H - self.nh) / 2 - 0.1))
+
+    @property
+    def frame(self):
+        return (self.r, self.r, float(self.left), float(self.top), float(self.w0), float(self.h0))
+
+    def plan(self, src=0, fill=MOSAIC_FILL):
+        """The MosaicPlan that draws it: one layer without stages, one tile."""
+        ly = MosaicLayer(self.H, self.W, fill=fill)
+        ly.tiles = [MosaicTile(src, self.h0, self.w0, self.nw, self.nh, self.left, self.top,
+                               (self.left, self.top, self.left + self.nw, self.top + self.nh))]
+        ly.applied.append("letterbox")
+        return MosaicPlan([ly])
+
+
+class Frames:
+    """A batch's frames: ``host`` [B, 6] float32 numpy, ``tensor`` the same on the device (None
+    without a device)."""
+
+    def __init__(self, rows, device):
+        self.host = np.asarray(rows, np.float32).reshape(-1, 6)
+        self.tensor = None if device is None else torch.from_numpy(self.host).to(device)
+
+
+def frames_stretch(sizes, size, device="cuda"):
+    """Frames of resize_normalize's plain stretch of originals ``sizes`` = [(h0, w0)] to ``size`` =
+    (H, W): gains W / w0 and H / h0, no padding."""
+    H, W = size
+    return Frames([(W / w0, H / h0, 0.0, 0.0, w0, h0) for h0, w0 in sizes], device)
+
+
+def letterbox_normalize(images, size, fill=MOSAIC_FILL, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype=torch.float32):
+    """Device HWC uint8 images (any sizes) -> ([B, 3, H, W] letterboxed, normalised batch, Frames), in
+    one yms_mosaic_normalize launch."""
+    if not images:
+        raise ValueError("yms: empty batch")
+    H, W = size
+    boxes = [Letterbox(im.shape[0], im.shape[1], H, W) for im in images]
+    out = mosaic_normalize([[im] for im in images], [lb.plan(0, fill) for lb in boxes], size, mean, std, dtype)
+    return out, Frames([lb.frame for lb in boxes], images[0].device)
+
+
 class COCODetection(torch.utils.data.Dataset):
     """dataset.py COCODataset's data source (image list, category map, annotation filters) without
     pycocotools; ``__getitem__`` returns (decoded HWC uint8 image, [n, 5] targets for ``img_size``),
@@ -704,11 +774,15 @@ class COCODataset(COCODetection):
     so a change reaches them only through a new iterator / DataLoader."""
 
     def __init__(self, images_dir, annotations_file, transform_params=None, is_train=True, img_size=(640, 640),
-                 num_classes=80, seed=0, mosaic=False):
+                 num_classes=80, seed=0, mosaic=False, letterbox=False):
         super().__init__(images_dir, annotations_file, img_size=img_size, num_classes=num_classes, seed=seed)
         self.transform_params = dict(transform_params or {})
         self.is_train = is_train
         self.mosaic = mosaic
+        # evaluation only (is_train=False): __getitem__ -> (image, [n, 5] targets = (class, x1, y1, x2, y2)
+        # in ORIGINAL-image pixels, Letterbox), and collate_to_gpu returns the batch's Frames as a third
+        # value -- detections un-letterboxed by yms.ops.detect(frames=...) are compared with these targets
+        self.letterbox = letterbox
 
     def _load(self, idx):
         from PIL import Image
@@ -746,6 +820,10 @@ class COCODataset(COCODetection):
             return images, mosaic_targets(plan, anns), plan
         image, (boxes, labels) = self._load(idx)
         h0, w0 = image.shape[:2]
+        if self.letterbox and not self.is_train:
+            rows = [[c, x, y, x + w, y + h] for (x, y, w, h), c in zip(boxes, labels)]
+            t = torch.tensor(rows, dtype=torch.float32) if rows else torch.empty(0, 5)
+            return image, t, Letterbox(h0, w0, self.img_h, self.img_w)
         plan = sample_augmentation(rng, tp, h0, w0, self.img_h, self.img_w, self.is_train)
         return image, transform_boxes(boxes, labels, plan), plan
 
@@ -767,8 +845,13 @@ def collate_targets(batch):
 def collate_to_gpu(batch, img_size, device, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """dataset.py collate_fn output on the GPU: ([B, 3, H, W] normalised images, [M, 6] targets).
     A batch with at least one mosaic sample goes through mosaic_normalize whole (its plain samples
-    as degenerate records: still one launch); any other batch takes the paths it took before."""
+    as degenerate records: still one launch); any other batch takes the paths it took before.
+    A batch of COCODataset(is_train=False, letterbox=True) samples is letterboxed instead and comes
+    back as (images, [M, 6] targets = (image, class, x1, y1, x2, y2) in original pixels, Frames)."""
     images, extra, targets = collate_targets(batch)
+    if extra and all(isinstance(e, Letterbox) for e in extra):     # COCODataset(is_train=False, letterbox=True)
+        x, frames = letterbox_normalize(to_device(images, device), img_size, MOSAIC_FILL, mean, std, dtype)
+        return x, targets.to(device, non_blocking=True), frames
     if any(isinstance(e, MosaicPlan) for e in extra):
         dev_images = [to_device(im, device) if isinstance(im, (list, tuple)) else to_device([im], device)[0]
                       for im in images]

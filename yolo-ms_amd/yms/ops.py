@@ -1,6 +1,7 @@
 """Functional HIP ops outside the module graph: torchvision-compatible NMS, the
-reference's batched post-process (train.py:63-113 / tools/test.py:166-218) and the
-standalone DFL integral.  GPU tensors only; every call goes through libyms.so."""
+reference's batched post-process (train.py:63-113 / tools/test.py:166-218), the opt-in
+COCO-protocol post-process around the same NMS (``detect``) and the standalone DFL integral.
+GPU tensors only; every call goes through libyms.so."""
 from __future__ import annotations
 
 import ctypes
@@ -45,9 +46,15 @@ def _nms_ws(dev, B, A, nc, iou):
     gmin = int(os.environ.get("YMS_NMS_GRAPH_MIN", "2048"))
     full = iou >= 0.0 and gmin > 0 and A >= max(gmin, 32)
     nbytes = (L.lib().yms_nms_ws_bytes if full else L.lib().yms_nms_ws_bytes_min)(B, A, nc)
-    cache = getattr(_TLS, "nms_ws", None)
+    return _cached_ws("nms_ws", dev, nbytes), nbytes
+
+
+def _cached_ws(slot, dev, nbytes):
+    """The calling thread's scratch buffer `slot` for (device, current stream), grown on demand."""
+    cache = getattr(_TLS, slot, None)
     if cache is None:
-        cache = _TLS.nms_ws = {}
+        cache = {}
+        setattr(_TLS, slot, cache)
     key = (dev.index, L.stream_ptr(dev))
     ws = cache.get(key)
     if ws is None or ws.numel() < nbytes:
@@ -55,7 +62,7 @@ def _nms_ws(dev, B, A, nc, iou):
             cache.pop(next(iter(cache)))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         cache[key] = ws
-    return ws, nbytes
+    return ws
 
 
 def nms(boxes, scores, iou_threshold):
@@ -114,3 +121,116 @@ def postprocess(pred, conf_thresh=0.25, iou_thresh=0.45):
         out.append({"boxes": bxy[b].index_select(0, idx), "scores": score[b].index_select(0, idx),
                     "labels": klbl[b, :k].long()})
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# COCO-protocol detect (csrc/detect.hip): candidates -> NMS -> finalize, no host sync
+# ------------------------------------------------------------------------------------------
+MAX_NMS_LIMIT, MAX_DET_LIMIT, MAX_CLASSES = 65536, 1024, 1024
+_MASKS = {}
+
+
+class Detections:
+    """detect()'s result, all on the device and padded to max_det rows per image (rows beyond
+    counts[b] are zero with label / anchor -1): boxes [B, max_det, 4] fp32 xyxy, scores [B, max_det],
+    labels and anchors [B, max_det] int32, counts [B] int32, candidates [B] int32 (the image's
+    candidates before the max_nms cap)."""
+    __slots__ = ("boxes", "scores", "labels", "anchors", "counts", "candidates")
+
+    def __init__(self, boxes, scores, labels, anchors, counts, candidates):
+        self.boxes, self.scores, self.labels, self.anchors = boxes, scores, labels, anchors
+        self.counts, self.candidates = counts, candidates
+
+    def to_list(self):
+        """The one host sync: per image {'boxes' [k, 4], 'scores' [k], 'labels' [k] int64}, what
+        yms.metrics.MeanAveragePrecision.update takes."""
+        return [{"boxes": self.boxes[b, :k], "scores": self.scores[b, :k], "labels": self.labels[b, :k].long()}
+                for b, k in enumerate(self.counts.cpu().tolist())]
+
+
+def _class_mask(dev, nc, classes):
+    """Device uint8 [nc] mask of the class subset, cached so that a repeated call copies nothing."""
+    key = (dev.index, nc, classes)
+    m = _MASKS.get(key)
+    if m is None:
+        if len(_MASKS) >= 64:
+            _MASKS.pop(next(iter(_MASKS)))
+        host = torch.zeros(nc, dtype=torch.uint8)
+        host[list(classes)] = 1
+        m = _MASKS[key] = host.to(dev)
+    return m
+
+
+def detect(pred, conf=0.25, iou=0.45, *, multi_label=False, agnostic=False, classes=None, max_det=300,
+           max_nms=30000, frames=None):
+    """The post-process of the published YOLOv8 / YOLO-MS AP protocol on decoded predictions
+    [B, A, 4+nc] (fp32; (cx, cy, w, h) in input pixels + class scores) -> :class:`Detections`.
+
+    Candidates are every (anchor, class) with score > conf (``multi_label``) or each anchor's best
+    class (ties to the lower class) when it is > conf; ``classes`` keeps a subset (in best-class mode
+    after the arg-max, as ultralytics filters).  At most ``max_nms`` candidates per image go to the
+    NMS, by (score descending, anchor ascending, class ascending); the NMS is class-wise, or
+    class-agnostic with ``agnostic``; at most ``max_det`` detections come out, by (score descending,
+    candidate row ascending, rows being in ascending anchor * nc + class order).  ``frames``: a
+    [B, 6] device tensor (gain_x, gain_y, pad_x, pad_y, w0, h0) -- or yms.data's Frames -- maps the
+    boxes back to each original image, min(max((v - pad) / gain, 0), w0 | h0); boxes wholly in the
+    padding stay, with zero area.  These tie rules are this package's; ultralytics leaves ties to
+    its sort (parity UNPINNED).  No host synchronisation; ``Detections.to_list()`` is the one sync."""
+    _cuda(pred)
+    if pred.dim() != 3 or pred.shape[2] < 5 or pred.shape[0] < 1 or pred.shape[1] < 1:
+        raise ValueError(f"yms: detect expects [B, A, 4+nc] predictions, got {tuple(pred.shape)}")
+    B, A, no = pred.shape
+    nc = no - 4
+    conf, iou = float(conf), float(iou)
+    if not conf >= 0.0:
+        raise ValueError("yms: detect needs conf >= 0 (scores are ordered by their bit patterns)")
+    if not 1 <= int(max_nms) <= MAX_NMS_LIMIT:
+        raise ValueError(f"yms: max_nms must be in 1..{MAX_NMS_LIMIT}")
+    if not 1 <= int(max_det) <= MAX_DET_LIMIT:
+        raise ValueError(f"yms: max_det must be in 1..{MAX_DET_LIMIT}")
+    if nc > MAX_CLASSES or A * nc >= 2 ** 31:
+        raise ValueError(f"yms: detect handles at most {MAX_CLASSES} classes and A * nc < 2^31")
+    dev = pred.device
+    mask = None
+    if classes is not None:
+        classes = tuple(sorted({int(c) for c in classes}))
+        if any(c < 0 or c >= nc for c in classes):
+            raise ValueError(f"yms: classes must be a subset of [0, {nc})")
+        mask = _class_mask(dev, nc, classes)
+    if frames is not None:
+        frames = getattr(frames, "tensor", frames)
+        _cuda(frames)
+        if tuple(frames.shape) != (B, 6) or frames.dtype != torch.float32 or frames.device != dev:
+            raise ValueError("yms: frames must be a [B, 6] fp32 tensor on the predictions' device")
+        frames = frames.contiguous()
+    max_det = int(max_det)
+    # no image has more candidates than pairs: rows beyond that would only ever be fill
+    K = min(int(max_nms), A * nc if multi_label else A)
+    p = pred.detach().float().contiguous()
+    st = L.stream_ptr(dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    cbox = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    cscore = torch.empty((B, K), dtype=torch.float32, device=dev)
+    clabel = torch.empty((B, K), **i32)
+    canchor = torch.empty((B, K), **i32)
+    ccount = torch.empty(B, **i32)
+    ctotal = torch.empty(B, **i32)
+    wsb = L.lib().yms_det_ws_bytes(B, A, nc, K)
+    ws = _cached_ws("det_ws", dev, wsb)
+    L.call("yms_det_candidates", B, A, nc, p.data_ptr(), ctypes.c_float(conf), int(bool(multi_label)), L.ptr(mask),
+           K, cbox.data_ptr(), cscore.data_ptr(), clabel.data_ptr(), canchor.data_ptr(), ccount.data_ptr(),
+           ctotal.data_ptr(), ws.data_ptr(), wsb, st)
+    # class-agnostic: every live row is class 0 of one class; the true labels stay in clabel
+    nlabel, nnc = (clabel.clamp(max=0), 1) if agnostic else (clabel, nc)
+    keep = torch.empty((B, K), dtype=torch.int64, device=dev)
+    kcount = torch.empty(B, **i32)
+    nws, nwsb = _nms_ws(dev, B, K, nnc, iou)
+    L.call("yms_nms_classwise", B, K, nnc, cbox.data_ptr(), cscore.data_ptr(), nlabel.data_ptr(),
+           ctypes.c_double(iou), keep.data_ptr(), None, kcount.data_ptr(), nws.data_ptr(), nwsb, st)
+    det = torch.empty((B, max_det, 6), dtype=torch.float32, device=dev)
+    danchor = torch.empty((B, max_det), **i32)
+    dcount = torch.empty(B, **i32)
+    L.call("yms_det_finalize", B, K, max_det, cbox.data_ptr(), cscore.data_ptr(), clabel.data_ptr(),
+           canchor.data_ptr(), keep.data_ptr(), kcount.data_ptr(), L.ptr(frames), det.data_ptr(),
+           danchor.data_ptr(), dcount.data_ptr(), st)
+    return Detections(det[..., :4], det[..., 4], det[..., 5].to(torch.int32), danchor, dcount, ctotal)
