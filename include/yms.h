@@ -451,6 +451,25 @@ yms_status yms_tal_loss(int dtype, int batch, int nc, int nlevels, const void* c
                         const float* lambdas, void* ws, size_t ws_bytes, float* out, int* assign_gt,
                         float* assign_score, void* stream);
 
+/* ---- dynamic soft-label assigner loss (opt-in; DESIGN.md "Dynamic soft-label loss") ---------- */
+/* YOLO-MS's own loss (the RTMDet recipe): dynamic soft-label assigner, Quality Focal Loss on the class
+ * logits, GIoU on the boxes, both weighted by the matched IoU; restated in tests/dsl_ref.py (the
+ * definition; parity with mmdet / mmyolo is not pinned).  Maps, targets, workspace and ignored rows
+ * as yms_tal_loss.  topk 1..13: the IoUs summed into a GT's dynamic k; radius, iou_weight >= 0 and
+ * beta >= 1, finite: the soft centre prior's radius in strides, the weight of -log(IoU) in the cost and
+ * the focal exponent (published 13, 3, 3, 2).  gains (host [3]) = box, cls, dfl gains (published 2, 1;
+ * the recipe has no DFL term: 0).  out (device fp32 [5]) = total, box, cls, dfl, norm with total =
+ * gains . terms and norm = max(sum of the soft labels, 1); grads = d(total)/d(maps).  assign_gt /
+ * assign_score: NULL or device [batch * anchors], the target row each anchor is assigned to (-1:
+ * background) and its soft label.  dynamic_k: NULL or device [n_targets], each row's dynamic k (0 for an
+ * ignored row and for a row of an image without candidates). */
+size_t yms_dsl_loss_ws_bytes(int batch, int anchors, int nc, int n_targets);
+yms_status yms_dsl_loss(int dtype, int batch, int nc, int nlevels, const void* const* maps, void* const* grads,
+                        const int* hs, const int* ws_, const float* strides, int ld, const float* targets,
+                        int n_targets, float img_w, float img_h, int topk, float radius, float iou_weight,
+                        float beta, const float* gains, void* ws, size_t ws_bytes, float* out, int* assign_gt,
+                        float* assign_score, int* dynamic_k, void* stream);
+
 /* ---- head decode + NMS ------------------------------------------------------------------- */
 /* Raw head maps lvl[i]: NHWC [n, h_i, w_i, no_ld] with channels (64 DFL box logits, nc cls
  * logits).  out: [n, A, 4+nc] fp32 = (cx, cy, w, h)*stride_i, sigmoid(cls).  When nms_score

@@ -1,10 +1,11 @@
-"""Dev tool: the two detection losses in isolation -- yms_tal_loss (task-aligned assigner, opt-in) and
-yms_det_loss (the reference's ComputeLoss) alternated in one process on the same head maps: B=64,
+"""Dev tool: the detection losses in isolation -- yms_tal_loss (task-aligned assigner, opt-in),
+yms_dsl_loss (dynamic soft-label assigner + QFL + GIoU, YOLO-MS's own, opt-in) and yms_det_loss (the
+reference's ComputeLoss) alternated in one process on the same head maps: B=64,
 640x640 (8400 anchors), nc=80, bf16 NHWC maps with channel stride 144, value + gradient, 8 and 40
 GTs per image.  Maps, gradients, targets and workspaces are allocated once; the timed work is the
 launches only, between device events, in windows of at least 0.5 s after a warm-up.  Prints ms per
 call, the algorithmic bytes (maps read once + gradient written once) and the bytes/s achieved.
-Usage: python tools/loss_micro.py [--rounds 3] [--batch 64] [--size 640] [--gts 8 40]"""
+Usage: python tools/loss_micro.py [--rounds 3] [--batch 64] [--size 640] [--gts 8 40] [--losses tal dsl det]"""
 import argparse
 import ctypes
 import os
@@ -24,6 +25,7 @@ def main():
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--nc", type=int, default=80)
     ap.add_argument("--gts", type=int, nargs="+", default=[8, 40])
+    ap.add_argument("--losses", nargs="+", default=["tal", "dsl", "det"], choices=["tal", "dsl", "det"])
     ap.add_argument("--window", type=float, default=0.5, help="least seconds per timed window")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -50,7 +52,8 @@ def main():
     hsa = (ctypes.c_int * n)(*hs)
     sta = (ctypes.c_float * n)(*strides)
     lam = (ctypes.c_float * 3)(7.5, 0.5, 1.5)
-    out = torch.empty(4, dtype=torch.float32, device=dev)
+    gains = (ctypes.c_float * 3)(2.0, 1.0, 0.0)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
     st = L.stream_ptr()
     code = L.dtype_code(dt)
     fS = ctypes.c_float(float(S))
@@ -69,9 +72,14 @@ def main():
         M = tg.shape[0]
         wt = torch.empty(L.lib().yms_tal_loss_ws_bytes(B, A, nc, M), dtype=torch.uint8, device=dev)
         wd = torch.empty(L.lib().yms_det_loss_ws_bytes(B, A, nc, M), dtype=torch.uint8, device=dev)
+        wq = torch.empty(L.lib().yms_dsl_loss_ws_bytes(B, A, nc, M), dtype=torch.uint8, device=dev)
         cases.append((f"tal gt{per_img}", lambda tg=tg, M=M, wt=wt: L.call(
             "yms_tal_loss", code, B, nc, n, mp, gp, hsa, hsa, sta, ld, tg.data_ptr(), M, fS, fS, 10,
             ctypes.c_float(0.5), ctypes.c_float(6.0), lam, wt.data_ptr(), wt.numel(), out.data_ptr(), None, None, st)))
+        cases.append((f"dsl gt{per_img}", lambda tg=tg, M=M, wq=wq: L.call(
+            "yms_dsl_loss", code, B, nc, n, mp, gp, hsa, hsa, sta, ld, tg.data_ptr(), M, fS, fS, 13,
+            ctypes.c_float(3.0), ctypes.c_float(3.0), ctypes.c_float(2.0), gains, wq.data_ptr(), wq.numel(),
+            out.data_ptr(), None, None, None, st)))
         cases.append((f"det gt{per_img}", lambda tg=tg, M=M, wd=wd: L.call(
             "yms_det_loss", code, B, nc, n, mp, gp, hsa, hsa, sta, ld, tg.data_ptr(), M, fS, fS, 3, None, lam,
             wd.data_ptr(), wd.numel(), out.data_ptr(), st)))
@@ -85,6 +93,7 @@ def main():
         e.synchronize()
         return s.elapsed_time(e) / k            # ms per call
 
+    cases = [(label, fn) for label, fn in cases if label.split()[0] in a.losses]
     iters = {}
     for label, fn in cases:                     # warm-up, then size the window from a short timed run
         for _ in range(5):

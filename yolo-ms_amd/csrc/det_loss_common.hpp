@@ -1,5 +1,5 @@
-// Device helpers shared by the two detection losses (det_loss.hip: the reference's ComputeLoss;
-// tal_loss.hip: the task-aligned assigner loss): head-map addressing, the DFL softmax, the IoU
+// Device helpers shared by the detection losses (det_loss.hip: the reference's ComputeLoss;
+// tal_loss.hip: the task-aligned assigner loss; dsl_loss.hip: the dynamic soft-label assigner loss): head-map addressing, the DFL softmax, the IoU
 // family with its analytic gradient, BCE-with-logits and the fixed-order block sum.
 #pragma once
 #include <cmath>
@@ -221,6 +221,112 @@ __device__ __forceinline__ void block_sum_store(float v, float* part, long slot)
   __syncthreads();
   if (threadIdx.x == 0) part[slot] = (s[0] + s[1]) + (s[2] + s[3]);
   __syncthreads();
+}
+
+// ---- shared by the anchor-based assigner losses (tal_loss.hip, dsl_loss.hip) ------------------
+constexpr float TAL_INSIDE_EPS = 1e-9f;
+constexpr float TAL_DFL_MAX = (float)(DL_DFL - 1) - 0.01f;
+
+// target row -> false when ignored (image outside [0, B) or class outside [0, nc)); image, class
+// and the GT's xyxy box in pixels
+__device__ __forceinline__ bool tal_row(const float* t, int B, int nc, float img_w, float img_h, int& b, int& cls,
+                                        float (&g)[4]) {
+  if (!(t[0] >= 0.f && t[0] < (float)B && t[1] >= 0.f && t[1] < (float)nc)) return false;
+  b = (int)t[0];
+  cls = (int)t[1];
+  const float gc[4] = {t[2] * img_w, t[3] * img_h, t[4] * img_w, t[5] * img_h};
+  cxcywh_to_xyxy(gc, g);
+  return true;
+}
+
+__device__ __forceinline__ bool tal_inside(float ax, float ay, const float (&g)[4]) {
+  return fminf(fminf(ax - g[0], ay - g[1]), fminf(g[2] - ax, g[3] - ay)) > TAL_INSIDE_EPS;
+}
+
+// block b of 256 threads: image b's valid target rows in target order -> rows[b * M ..], nrows[b]
+// (global memory, so no limit on the rows of one image)
+__device__ __forceinline__ void tal_list_rows(const float* tg, int M, int B, int nc, int* rows, int* nrows) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* mine = rows + (long)b * M;
+  __shared__ int wcnt[4];
+  int base = 0;
+  for (int j0 = 0; j0 < M; j0 += 256) {
+    const int j = j0 + tid;
+    bool hit = false;
+    if (j < M) {
+      const float* t = tg + (long)j * 6;
+      hit = t[0] >= 0.f && t[0] < (float)B && t[1] >= 0.f && t[1] < (float)nc && (int)t[0] == b;
+    }
+    const unsigned long long bal = __ballot(hit);
+    if ((tid & 63) == 0) wcnt[tid >> 6] = __popcll(bal);
+    __syncthreads();
+    int pos = base;
+    for (int q = 0; q < (tid >> 6); ++q) pos += wcnt[q];
+    if (hit) mine[pos + __popcll(bal & ((1ull << (tid & 63)) - 1ull))] = j;
+    base += (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+  }
+  if (tid == 0) nrows[b] = base;
+}
+
+// fixed-order fp64 sum of one value per thread over a 256-thread block -> every thread
+__device__ __forceinline__ double tal_block_sum(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// 1 - IoU-family value (IOU: box_iou_grad's iou_type) and the DFL value (1/4 of the sides' two-bin cross entropies) of one foreground anchor
+// and, GRAD, d/d logits scaled by sb, sd, left in v
+template <bool GRAD, int IOU>
+__device__ __forceinline__ void tal_box_dfl(float (&v)[4 * DL_DFL], float ax, float ay, float stride,
+                                            const float (&g)[4], float sb, float sd, float& lbox, float& ldfl) {
+  // DFL targets in stride units, clamped into the bins, read before the softmax
+  const float dist[4] = {ax - g[0], ay - g[1], g[2] - ax, g[3] - ay};
+  int li[4];
+  float wl[4], wr[4], xl[4], xr[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const float d = fminf(fmaxf(dist[s] / stride, 0.f), TAL_DFL_MAX);
+    const float fl = floorf(d);
+    wr[s] = d - fl;
+    wl[s] = 1.0f - wr[s];
+    li[s] = (int)fl;                    // 0..14: the right bin li + 1 <= 15
+    xl[s] = xr[s] = 0.f;
+#pragma unroll
+    for (int i = 0; i < DL_DFL; ++i) {  // selects, not a runtime index: v stays in registers
+      xl[s] = i == li[s] ? v[s * DL_DFL + i] : xl[s];
+      xr[s] = i == li[s] + 1 ? v[s * DL_DFL + i] : xr[s];
+    }
+  }
+  float e[4], lse[4];
+  dfl_softmax(v, e, lse);     // v: probabilities
+  const float p[4] = {ax - e[0] * stride, ay - e[1] * stride, ax + e[2] * stride, ay + e[3] * stride};
+  float dp[4];
+  lbox = 1.f - box_iou_grad<GRAD>(p, g, IOU, dp);
+  float dfl = 0.f;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) dfl += (lse[s] - xl[s]) * wl[s] + (lse[s] - xr[s]) * wr[s];
+  ldfl = 0.25f * dfl;
+  if (GRAD) {
+    // loss 1 - val -> d/dp = -dp; p0 = ax - e0 s (d/de0 = -s), p2 = ax + e2 s (d/de2 = s)
+    const float k = sb * stride;
+    const float ge[4] = {dp[0] * k, dp[1] * k, -dp[2] * k, -dp[3] * k};
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int i = 0; i < DL_DFL; ++i) {
+        const float pr = v[s * DL_DFL + i];
+        float gi = ge[s] * pr * ((float)i - e[s]);      // d e_s / d logit_i = p_i (i - e_s)
+        gi += sd * (pr - (i == li[s] ? wl[s] : 0.f) - (i == li[s] + 1 ? wr[s] : 0.f));
+        v[s * DL_DFL + i] = gi;
+      }
+  }
 }
 
 }  // namespace yms

@@ -34,25 +34,6 @@
 
 namespace yms {
 
-constexpr float TAL_INSIDE_EPS = 1e-9f;
-constexpr float TAL_DFL_MAX = (float)(DL_DFL - 1) - 0.01f;
-
-// target row -> false when ignored (image outside [0, B) or class outside [0, nc)); image, class
-// and the GT's xyxy box in pixels
-__device__ __forceinline__ bool tal_row(const float* t, int B, int nc, float img_w, float img_h, int& b, int& cls,
-                                        float (&g)[4]) {
-  if (!(t[0] >= 0.f && t[0] < (float)B && t[1] >= 0.f && t[1] < (float)nc)) return false;
-  b = (int)t[0];
-  cls = (int)t[1];
-  const float gc[4] = {t[2] * img_w, t[3] * img_h, t[4] * img_w, t[5] * img_h};
-  cxcywh_to_xyxy(gc, g);
-  return true;
-}
-
-__device__ __forceinline__ bool tal_inside(float ax, float ay, const float (&g)[4]) {
-  return fminf(fminf(ax - g[0], ay - g[1]), fminf(g[2] - ax, g[3] - ay)) > TAL_INSIDE_EPS;
-}
-
 // max(CIoU, 0) of the predicted box and the GT (NaN -> 0)
 __device__ __forceinline__ float tal_overlap(const float4 p4, const float (&g)[4]) {
   const float p[4] = {p4.x, p4.y, p4.z, p4.w};
@@ -195,27 +176,7 @@ __global__ __launch_bounds__(256) void tal_topk_kernel(LossLevels L, const float
 // per image: its valid target rows in target order -> rows[b * M ..], nrows[b] (global memory, so
 // no limit on the rows of one image)
 __global__ __launch_bounds__(256) void tal_rows_kernel(const float* tg, int M, int B, int nc, int* rows, int* nrows) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  int* mine = rows + (long)b * M;
-  __shared__ int wcnt[4];
-  int base = 0;
-  for (int j0 = 0; j0 < M; j0 += 256) {
-    const int j = j0 + tid;
-    bool hit = false;
-    if (j < M) {
-      const float* t = tg + (long)j * 6;
-      hit = t[0] >= 0.f && t[0] < (float)B && t[1] >= 0.f && t[1] < (float)nc && (int)t[0] == b;
-    }
-    const unsigned long long bal = __ballot(hit);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = __popcll(bal);
-    __syncthreads();
-    int pos = base;
-    for (int q = 0; q < (tid >> 6); ++q) pos += wcnt[q];
-    if (hit) mine[pos + __popcll(bal & ((1ull << (tid & 63)) - 1ull))] = j;
-    base += (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-    __syncthreads();
-  }
-  if (tid == 0) nrows[b] = base;
+  tal_list_rows(tg, M, B, nc, rows, nrows);
 }
 
 // per anchor: its final GT (agt: target row or -1), the pair's metric, the per-GT maxima
@@ -285,18 +246,6 @@ __global__ __launch_bounds__(256) void tal_score_kernel(const float* tg, int A, 
   block_sum_store(t, part, (long)b * gridDim.x + blockIdx.x);
 }
 
-// fixed-order fp64 sum of one value per thread over a 256-thread block -> every thread
-__device__ __forceinline__ double tal_block_sum(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 __global__ __launch_bounds__(256) void tal_tss_kernel(long n, const float* part, float* tss) {
   __shared__ double sh[256];
   double s = 0.0;
@@ -339,54 +288,6 @@ __global__ __launch_bounds__(256) void tal_cls_kernel(LossLevels L, int A, int n
   block_sum_store(acc, part, (long)b * gridDim.x + blockIdx.x);
 }
 
-// 1 - CIoU and the DFL value (1/4 of the sides' two-bin cross entropies) of one foreground anchor
-// and, GRAD, d/d logits scaled by sb, sd, left in v
-template <bool GRAD>
-__device__ __forceinline__ void tal_box_dfl(float (&v)[4 * DL_DFL], float ax, float ay, float stride,
-                                            const float (&g)[4], float sb, float sd, float& lbox, float& ldfl) {
-  // DFL targets in stride units, clamped into the bins, read before the softmax
-  const float dist[4] = {ax - g[0], ay - g[1], g[2] - ax, g[3] - ay};
-  int li[4];
-  float wl[4], wr[4], xl[4], xr[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float d = fminf(fmaxf(dist[s] / stride, 0.f), TAL_DFL_MAX);
-    const float fl = floorf(d);
-    wr[s] = d - fl;
-    wl[s] = 1.0f - wr[s];
-    li[s] = (int)fl;                    // 0..14: the right bin li + 1 <= 15
-    xl[s] = xr[s] = 0.f;
-#pragma unroll
-    for (int i = 0; i < DL_DFL; ++i) {  // selects, not a runtime index: v stays in registers
-      xl[s] = i == li[s] ? v[s * DL_DFL + i] : xl[s];
-      xr[s] = i == li[s] + 1 ? v[s * DL_DFL + i] : xr[s];
-    }
-  }
-  float e[4], lse[4];
-  dfl_softmax(v, e, lse);     // v: probabilities
-  const float p[4] = {ax - e[0] * stride, ay - e[1] * stride, ax + e[2] * stride, ay + e[3] * stride};
-  float dp[4];
-  lbox = 1.f - box_iou_grad<GRAD>(p, g, 3, dp);
-  float dfl = 0.f;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) dfl += (lse[s] - xl[s]) * wl[s] + (lse[s] - xr[s]) * wr[s];
-  ldfl = 0.25f * dfl;
-  if (GRAD) {
-    // loss 1 - val -> d/dp = -dp; p0 = ax - e0 s (d/de0 = -s), p2 = ax + e2 s (d/de2 = s)
-    const float k = sb * stride;
-    const float ge[4] = {dp[0] * k, dp[1] * k, -dp[2] * k, -dp[3] * k};
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < DL_DFL; ++i) {
-        const float pr = v[s * DL_DFL + i];
-        float gi = ge[s] * pr * ((float)i - e[s]);      // d e_s / d logit_i = p_i (i - e_s)
-        gi += sd * (pr - (i == li[s] ? wl[s] : 0.f) - (i == li[s] + 1 ? wr[s] : 0.f));
-        v[s * DL_DFL + i] = gi;
-      }
-  }
-}
-
 // per anchor: weighted box and DFL sums and, GRAD, their gradient into the 64 DFL logits
 template <typename T, bool GRAD>
 __global__ __launch_bounds__(256) void tal_box_kernel(LossLevels L, const float* tg, int M, int B, int A, int nc,
@@ -410,7 +311,7 @@ __global__ __launch_bounds__(256) void tal_box_kernel(LossLevels L, const float*
       const float t = tsc[i];
       const float it = GRAD ? t / tss[0] : 0.f;
       float vb, vd;
-      tal_box_dfl<GRAD>(v, ax, ay, L.stride[l], g, nbox * it, ndfl * it, vb, vd);
+      tal_box_dfl<GRAD, 3>(v, ax, ay, L.stride[l], g, nbox * it, ndfl * it, vb, vd);
       lb = vb * t;
       ld = vd * t;
     }

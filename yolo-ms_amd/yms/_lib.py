@@ -187,6 +187,9 @@ _SIGS = {
     "yms_tal_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "yms_tal_loss": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _P, _P, _SZ, _P, _P, _P,
                           _P]),
+    "yms_dsl_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "yms_dsl_loss": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _F, _P, _P, _SZ, _P, _P,
+                          _P, _P, _P]),
     "yms_head_decode": (_I, [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P]),
     "yms_dfl": (_I, [_I, _I, _I, _I, _P, _P, _P]),
     "yms_nms_prep": (_I, [_I, _I, _I, _P, _F, _P, _P, _P, _P]),
