@@ -107,6 +107,12 @@ int yms_conv_stats_ld(const yms_conv_shape* s);
  * queries; returns the previous setting.  It changes yms_conv_stats_rows, so callers flip it only
  * while no plan sized under the other setting is in use (tests and A/B runs). */
 int yms_conv_direct_set(int on);
+/* Process-wide CU count that sizes the persistent grids, strip lengths, units per block and split-K
+ * counts of the conv, depthwise and weight-gradient kernels.  n > 0: that count from now on; n == 0:
+ * back to the device's; n < 0: query only.  Returns the previous setting (0 = the device's).  It
+ * changes yms_conv_stats_rows, yms_conv_dgrad_bnred_rows and the *_wgrad_ws_bytes queries, so callers
+ * flip it only while no plan sized under another setting is in use (tests and A/B runs). */
+int yms_cu_count_set(int n);
 /* Forward.  stats == NULL: y = act(conv(x)*scale[c] + shift[c]) (+ res) (scale/shift may
  * be NULL = identity).  stats != NULL (training): y = conv(x) (pre-BN z) and statistics rows
  * (sum z, sum (z - row mean)^2, pixel count) into stats. */

@@ -197,9 +197,9 @@ def test_full_model_fp32_grads_vs_fp64_oracle():
     assert worst < 1e-3, worst
 
 
-@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
-def test_c2f_lowp_train_grads(dt):
-    """Shallow block in bf16/fp16 training: forward, input and parameter grads within 3e-2 of fp32."""
+def c2f_lowp_train_grads(dt):
+    """Shallow block in bf16/fp16 training: forward, input and parameter grads within 3e-2 of fp32.  (Also run
+    by test_tile_walk_gpu.py with the grids sized for one CU.)"""
     torch.manual_seed(0)
     m = _closed_form_local(C.C2f(64, 64, 2)).to(DEV).train()
     x = torch.randn(4, 64, 20, 20, generator=torch.Generator().manual_seed(2))
@@ -220,6 +220,11 @@ def test_c2f_lowp_train_grads(dt):
     for k, t in pr.items():
         if t.grad is not None:
             assert _rel(pd[k[4:]].grad, t.grad) < 3e-2, k
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_c2f_lowp_train_grads(dt):
+    c2f_lowp_train_grads(dt)
 
 
 def test_cpu_tensor_fails_loudly():

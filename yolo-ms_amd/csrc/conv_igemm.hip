@@ -1475,7 +1475,12 @@ static void launch_wgrad(const TTParams& p, int bm, int bn, dim3 grid, hipStream
 
 }  // namespace yms
 
+// yms_cu_count_set's override (0 = none) sits in front of the cached device value: every geometry
+// decision calls conv_cu_count() at call time and no memo is keyed on it.
+static int cu_override = 0;
+
 int yms::conv_cu_count() {
+  if (cu_override > 0) return cu_override;
   static int n = 0;
   if (n == 0) {
     int dev = 0;
@@ -1484,6 +1489,12 @@ int yms::conv_cu_count() {
       n = 256;
   }
   return n;
+}
+
+extern "C" int yms_cu_count_set(int n) {
+  const int prev = cu_override;
+  if (n >= 0) cu_override = n;
+  return prev;
 }
 
 using namespace yms;

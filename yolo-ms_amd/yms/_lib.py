@@ -118,6 +118,7 @@ _SIGS = {
     "yms_conv_stats_rows": (_I, [_SP]),
     "yms_conv_stats_ld": (_I, [_SP]),
     "yms_conv_direct_set": (_I, [_I]),
+    "yms_cu_count_set": (_I, [_I]),
     "yms_conv_fwd": (_I, [_SP, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
     "yms_conv_stem_supported": (_I, [_SP]),
     "yms_conv_stem_stats_rows": (_I, [_SP]),
