@@ -385,6 +385,39 @@ yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, c
 yms_status yms_map_accumulate_coco(int n_det, const float* scores, const int* labels, const int* image,
                                    const int* rank, const uint16_t* matched, const uint16_t* ignored, int n_thr,
                                    int n_classes, const int* npig, double* precision, double* recall);
+/* ---- COCO AP on the device: from yms.ops.detect's padded output to the tables, no host read ---- */
+/* GPU: the matching of yms_map_match_coco on the padded layout, written into epoch buffers.  Inputs:
+ * det_boxes [n_images][max_det][4] xyxy, det_scores / det_labels [n_images][max_det], det_count
+ * [n_images] (max_det 1..1024; rows at or beyond an image's count are not read); gt_boxes
+ * [n_images][max_gt][4], gt_labels [n_images][max_gt], gt_count [n_images] (max_gt 0..2048, else
+ * YMS_ERR_UNSUPPORTED).  A device count above its padded width is clamped to it.  iou_thrs: HOST
+ * array, n_thr 1..16, as yms_map_match_coco; n_classes 1..4096.
+ * Outputs: epoch buffers of cap rows, of which this call owns [row0, row0 + n_images * max_det) and
+ * writes every one: score / label / rank [cap], matched / ignored [4][cap] (area-major, stride cap,
+ * bit t = threshold t).  A live row holds its score, its label and exactly yms_map_match_coco's rank
+ * and masks for the same image; a dead row (slot >= count) score 0, label -1, rank -1, zero masks.
+ *   npig[n_classes][4] += the ground truths of each class that are inside each area range (integer
+ *   atomics; a label outside [0, n_classes) is skipped).  The caller zeroes it once per epoch.
+ *   order_ws: n_images * max_det ints of scratch. */
+yms_status yms_map_match_coco_fixed(int n_images, int max_det, const float* det_boxes, const float* det_scores,
+                                    const int* det_labels, const int* det_count, int max_gt, const float* gt_boxes,
+                                    const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
+                                    int n_classes, long cap, long row0, float* score, int* label, int* rank,
+                                    uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws, void* stream);
+/* GPU: yms_map_accumulate_coco over the first n_rows rows of those epoch buffers (cap: the masks'
+ * area stride; image = row / max_det, so row order is the host's (image, index) order) -> DEVICE
+ * precision[n_thr][101][n_classes][4][3] and recall[n_thr][n_classes][4][3], float64, bit-identical
+ * to the host function: a row takes part when 0 <= rank < 100 and 0 <= label < n_classes, within a
+ * class the order is (score descending, row ascending).  Stream-ordered, no allocation, no read-back,
+ * integer atomics only (the result does not depend on scheduling), and a launch sequence fixed by
+ * (n_rows, n_classes).  NaN scores are outside the contract (they sort somewhere; nothing is indexed
+ * by them).  ws: yms_map_accumulate_coco_dev_ws_bytes(n_rows, n_thr, n_classes) bytes (never 0),
+ * 256-byte aligned; it holds the sort's key / row ping-pong buffers and digit counts. */
+size_t yms_map_accumulate_coco_dev_ws_bytes(long n_rows, int n_thr, int n_classes);
+yms_status yms_map_accumulate_coco_dev(long n_rows, long cap, const float* score, const int* label, const int* rank,
+                                       const uint16_t* matched, const uint16_t* ignored, int n_thr, int n_classes,
+                                       const int* npig, double* precision, double* recall, void* ws, size_t ws_bytes,
+                                       void* stream);
 
 /* ---- input pipeline ------------------------------------------------------ */
 /* dataset.py:132-134 per-sample A.Resize(INTER_LINEAR) + A.Normalize(mean, std) + ToTensorV2 and

@@ -14,6 +14,8 @@
 // lane, with COCOeval's ignore rules (out-of-range ground truths are visited last and only taken when
 // no in-range one qualifies; a detection matched to one, or unmatched and itself out of range, is
 // ignored); yms_map_accumulate_coco fills COCOeval's precision / recall tables on the host.
+// map_match_coco_fixed_kernel is the same matching on yms.ops.detect's padded layout, written into the
+// epoch buffers that csrc/map_accum.hip accumulates on the device.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -121,6 +123,8 @@ __global__ __launch_bounds__(64) void map_match_kernel(const float* dbox, const 
 constexpr int MAP_MAX_THR = 16;
 constexpr int MAP_N_AREA = 4;
 constexpr int MAP_COCO_WAVES = 4;
+constexpr int MAP_FIXED_MAX_DET = 1024;      // padded rows per image (yms.ops.detect's max_det limit)
+constexpr int MAP_MAX_CLASSES = 4096;
 
 struct MapCocoThr {
   double thr[MAP_MAX_THR];
@@ -159,10 +163,13 @@ __device__ __forceinline__ double map_iou_xywh(double bx, double by, double bw, 
 // (later one on ties) and takes the in-range one if there is any (COCOeval's break).  The "already
 // matched" bits are one LDS word column per lane (gm[wave][word][lane]): no lane shares a word, and
 // classes own disjoint bits, so they are cleared once.  There is no barrier after the setup.
-__global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
-    const float* dbox, const float* dscore, const int* dlabel, const int* doff, const float* gbox, const int* glabel,
-    const int* goff, MapCocoThr P, long n_det, uint16_t* dmatch, uint16_t* dign, uint8_t* gign_out, int* rank_out,
-    int* order_ws) {
+// The body is shared by the two layouts (prefix offsets / padded rows): every pointer is the image's
+// own first detection / ground truth, nd / ng its counts, mstride the masks' area stride.
+__device__ __forceinline__ void map_match_coco_image(const float* dbox, const float* dscore, const int* dlabel,
+                                                     int nd, const float* gbox, const int* glabel, int ng,
+                                                     const MapCocoThr& P, long mstride, uint16_t* dmatch,
+                                                     uint16_t* dign, uint8_t* gign_out, int* rank_out,
+                                                     int* order_ws) {
   __shared__ double gb[MAP_MAX_GT][4];
   __shared__ int gl[MAP_MAX_GT];
   __shared__ int heads[MAP_MAX_GT];
@@ -170,22 +177,20 @@ __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
   __shared__ unsigned gm[MAP_COCO_WAVES][MAP_MAX_GT / 32][64];
   __shared__ int n_heads;
   constexpr int NT = 64 * MAP_COCO_WAVES;
-  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d0 = doff[img], nd = doff[img + 1] - d0;
-  const int g0 = goff[img], ng = goff[img + 1] - g0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (ng > MAP_MAX_GT) return;            // the host entry point refuses these; never index past the LDS arrays
   const int T = P.n;
   const unsigned tmask = (1u << T) - 1u;
   if (tid == 0) n_heads = 0;
   // ground truths -> LDS in (class, input index) order, with their area-ignore bits
   for (int j = tid; j < ng; j += NT) {
-    const int lab = glabel[g0 + j];
+    const int lab = glabel[j];
     int p = 0;
     for (int i = 0; i < ng; ++i) {
-      const int li = glabel[g0 + i];
+      const int li = glabel[i];
       p += (li < lab || (li == lab && i < j)) ? 1 : 0;
     }
-    const float* q = gbox + (long)(g0 + j) * 4;
+    const float* q = gbox + (long)j * 4;
     const double gw = (double)(q[2] - q[0]), gh = (double)(q[3] - q[1]);   // width / height in fp32, as box_convert
     gb[p][0] = (double)q[0];
     gb[p][1] = (double)q[1];
@@ -194,30 +199,30 @@ __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
     gl[p] = lab;
     const unsigned bits = map_area_out_bits(gw * gh);
     gig[p] = (uint8_t)bits;
-    gign_out[g0 + j] = (uint8_t)bits;
+    if (gign_out) gign_out[j] = (uint8_t)bits;
   }
   for (int w = 0; w < (ng + 31) / 32; ++w) gm[wave][w][lane] = 0u;
   // detections: rank within the class (stable descending score), position in (class, rank) order,
   // and the masks of an unmatched detection (classes without ground truth here keep them)
   for (int d = tid; d < nd; d += NT) {
-    const int lab = dlabel[d0 + d];
-    const float sc = dscore[d0 + d];
+    const int lab = dlabel[d];
+    const float sc = dscore[d];
     int r = 0, below = 0;
     for (int j = 0; j < nd; ++j) {
-      const int lj = dlabel[d0 + j];
+      const int lj = dlabel[j];
       below += lj < lab ? 1 : 0;
       if (lj != lab) continue;
-      const float sj = dscore[d0 + j];
+      const float sj = dscore[j];
       r += (sj > sc || (sj == sc && j < d)) ? 1 : 0;
     }
-    rank_out[d0 + d] = r;
-    order_ws[d0 + below + r] = d;
-    const float* bp = dbox + (long)(d0 + d) * 4;
+    rank_out[d] = r;
+    order_ws[below + r] = d;
+    const float* bp = dbox + (long)d * 4;
     const unsigned out = map_area_out_bits((double)(bp[2] - bp[0]) * (double)(bp[3] - bp[1]));
 #pragma unroll
     for (int a = 0; a < MAP_N_AREA; ++a) {
-      dmatch[a * n_det + d0 + d] = 0;
-      dign[a * n_det + d0 + d] = (uint16_t)(((out >> a) & 1u) ? tmask : 0u);
+      dmatch[a * mstride + d] = 0;
+      dign[a * mstride + d] = (uint16_t)(((out >> a) & 1u) ? tmask : 0u);
     }
   }
   __syncthreads();
@@ -240,15 +245,15 @@ __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
     }
     int ds = 0, dn = 0;
     for (int base = 0; base < nd; base += 64) {
-      const int lj = base + lane < nd ? dlabel[d0 + base + lane] : 0x7fffffff;
+      const int lj = base + lane < nd ? dlabel[base + lane] : 0x7fffffff;
       ds += __popcll(__ballot(lj < c));
       dn += __popcll(__ballot(lj == c));
     }
     const int nr = min(dn, MAP_MAXDET);
     for (int r = 0; r < nr; ++r) {
-      const int d = order_ws[d0 + ds + r];
+      const int d = order_ws[ds + r];
       if ((unsigned)d >= (unsigned)nd) continue;      // NaN scores leave holes in the order: never index by one
-      const float* bp = dbox + (long)(d0 + d) * 4;
+      const float* bp = dbox + (long)d * 4;
       const double bx = (double)bp[0], by = (double)bp[1];
       const double bw = (double)(bp[2] - bp[0]), bh = (double)(bp[3] - bp[1]);
       const bool d_out = (map_area_out_bits(bw * bh) >> a) & 1u;
@@ -278,11 +283,62 @@ __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
       const bool ign = live && (matched ? jn < 0 : d_out);
       const unsigned long long bm = __ballot(matched), bi = __ballot(ign);
       if (lane < MAP_N_AREA) {
-        dmatch[lane * n_det + d0 + d] = (uint16_t)((bm >> (16 * lane)) & 0xffffull);
-        dign[lane * n_det + d0 + d] = (uint16_t)((bi >> (16 * lane)) & 0xffffull);
+        dmatch[lane * mstride + d] = (uint16_t)((bm >> (16 * lane)) & 0xffffull);
+        dign[lane * mstride + d] = (uint16_t)((bi >> (16 * lane)) & 0xffffull);
       }
     }
   }
+}
+
+__global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
+    const float* dbox, const float* dscore, const int* dlabel, const int* doff, const float* gbox, const int* glabel,
+    const int* goff, MapCocoThr P, long n_det, uint16_t* dmatch, uint16_t* dign, uint8_t* gign_out, int* rank_out,
+    int* order_ws) {
+  const int img = blockIdx.x;
+  const int d0 = doff[img], nd = doff[img + 1] - d0;
+  const int g0 = goff[img], ng = goff[img + 1] - g0;
+  map_match_coco_image(dbox + (long)d0 * 4, dscore + d0, dlabel + d0, nd, gbox + (long)g0 * 4, glabel + g0, ng, P,
+                       n_det, dmatch + d0, dign + d0, gign_out + g0, rank_out + d0, order_ws + d0);
+}
+
+// The padded layout of yms.ops.detect: image i owns rows [i * max_det, (i + 1) * max_det) of the inputs and
+// rows row0 + the same of the epoch buffers (masks: area stride cap).  Counts are read on the device and
+// clamped to the padded widths.  Every owned row is written: dead rows (slot >= count) get score 0, label -1,
+// rank -1 and zero masks; live rows the shared matching's results plus a copy of their score and label.
+// npig[class][area] += the image's ground truths that are in range (integer atomics).
+__global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_fixed_kernel(
+    const float* dbox, const float* dscore, const int* dlabel, const int* dcount, int max_det, const float* gbox,
+    const int* glabel, const int* gcount, int max_gt, MapCocoThr P, int n_classes, long cap, long row0, float* score,
+    int* label, int* rank_out, uint16_t* dmatch, uint16_t* dign, int* npig, int* order_ws) {
+  constexpr int NT = 64 * MAP_COCO_WAVES;
+  const int img = blockIdx.x, tid = threadIdx.x;
+  const int nd = min(max(dcount[img], 0), max_det);
+  const int ng = min(max(gcount[img], 0), max_gt);
+  const long in0 = (long)img * max_det, out0 = row0 + in0, gin0 = (long)img * max_gt;
+  for (int d = tid; d < max_det; d += NT) {
+    const bool on = d < nd;
+    score[out0 + d] = on ? dscore[in0 + d] : 0.0f;
+    label[out0 + d] = on ? dlabel[in0 + d] : -1;
+    if (!on) {
+      rank_out[out0 + d] = -1;
+#pragma unroll
+      for (int a = 0; a < MAP_N_AREA; ++a) {
+        dmatch[a * cap + out0 + d] = 0;
+        dign[a * cap + out0 + d] = 0;
+      }
+    }
+  }
+  for (int j = tid; j < ng; j += NT) {
+    const int lab = glabel[gin0 + j];
+    if (lab < 0 || lab >= n_classes) continue;
+    const float* q = gbox + (gin0 + j) * 4;
+    const unsigned bits = map_area_out_bits((double)(q[2] - q[0]) * (double)(q[3] - q[1]));
+#pragma unroll
+    for (int a = 0; a < MAP_N_AREA; ++a)
+      if (!((bits >> a) & 1u)) atomicAdd(&npig[lab * MAP_N_AREA + a], 1);
+  }
+  map_match_coco_image(dbox + in0 * 4, dscore + in0, dlabel + in0, nd, gbox + gin0 * 4, glabel + gin0, ng, P, cap,
+                       dmatch + out0, dign + out0, nullptr, rank_out + out0, order_ws + in0);
 }
 
 }  // namespace yms
@@ -390,6 +446,33 @@ yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, c
   hipLaunchKernelGGL(map_match_coco_kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0,
                      (hipStream_t)stream, det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, P,
                      (long)n_det, matched, ignored, gt_ignore, rank_ws, rank_ws + n_det);
+  return launch_status();
+}
+
+// the same matching on yms.ops.detect's padded layout, written into the epoch buffers of the device evaluator
+yms_status yms_map_match_coco_fixed(int n_images, int max_det, const float* det_boxes, const float* det_scores,
+                                    const int* det_labels, const int* det_count, int max_gt, const float* gt_boxes,
+                                    const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
+                                    int n_classes, long cap, long row0, float* score, int* label, int* rank,
+                                    uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws, void* stream) {
+  if (n_thr < 1 || n_thr > MAP_MAX_THR || !iou_thrs) return YMS_ERR_INVALID;
+  MapCocoThr P;
+  for (int t = 0; t < MAP_MAX_THR; ++t) P.thr[t] = t < n_thr ? iou_thrs[t] : 2.0;
+  P.n = n_thr;
+  for (int t = 0; t < n_thr; ++t)
+    if (!(P.thr[t] > 0.0 && P.thr[t] <= 1.0) || (t > 0 && !(P.thr[t] > P.thr[t - 1]))) return YMS_ERR_INVALID;
+  if (max_det < 1 || max_det > MAP_FIXED_MAX_DET || n_classes < 1 || n_classes > MAP_MAX_CLASSES || max_gt < 0)
+    return YMS_ERR_INVALID;
+  if (max_gt > MAP_MAX_GT) return YMS_ERR_UNSUPPORTED;
+  if (n_images <= 0) return YMS_OK;
+  if (row0 < 0 || cap < 0 || row0 + (long)n_images * max_det > cap) return YMS_ERR_INVALID;
+  if (!det_boxes || !det_scores || !det_labels || !det_count || !gt_count || !score || !label || !rank || !matched ||
+      !ignored || !npig || !order_ws)
+    return YMS_ERR_INVALID;
+  if (max_gt > 0 && (!gt_boxes || !gt_labels)) return YMS_ERR_INVALID;
+  hipLaunchKernelGGL(map_match_coco_fixed_kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0,
+                     (hipStream_t)stream, det_boxes, det_scores, det_labels, det_count, max_det, gt_boxes, gt_labels,
+                     gt_count, max_gt, P, n_classes, cap, row0, score, label, rank, matched, ignored, npig, order_ws);
   return launch_status();
 }
 

@@ -176,6 +176,10 @@ _SIGS = {
     "yms_map_accumulate": (_I, [_I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "yms_map_match_coco": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P]),
     "yms_map_accumulate_coco": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "yms_map_match_coco_fixed": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _L, _L, _P, _P, _P, _P, _P,
+                                      _P, _P, _P]),
+    "yms_map_accumulate_coco_dev_ws_bytes": (_SZ, [_L, _I, _I]),
+    "yms_map_accumulate_coco_dev": (_I, [_L, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "yms_det_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "yms_stream_create_cu_subset": (_I, [_I, _I, ctypes.POINTER(ctypes.c_void_p)]),
     "yms_resize_normalize": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _P]),

@@ -14,6 +14,11 @@ rules), ``compute()`` fills COCOeval's precision[T][101][K][4][3] and recall[T][
 the host (``yms_map_accumulate_coco``, maxDets 1 / 10 / 100) and averages them into AP, AP50, AP75,
 APs/m/l and AR@1/10/100, ARs/m/l.
 
+``CocoEvaluator`` is the same COCO summary kept on the device from ``yms.ops.detect``'s padded
+``Detections`` to the tables: ``update()`` matches straight into epoch buffers without a host
+synchronisation (``yms_map_match_coco_fixed``), ``compute()`` sorts and accumulates on the GPU
+(``yms_map_accumulate_coco_dev``, bit-identical tables) and reads the result back once.
+
 COCOeval semantics throughout; parity is against the restatements oracle/map_ref.py and
 tests/cocoeval_ref.py (torchmetrics / pycocotools are not installed: unpinned)."""
 from __future__ import annotations
@@ -191,3 +196,209 @@ class MeanAveragePrecision:
             "classes": torch.tensor(np.unique(np.concatenate(
                 [np.zeros(0, np.int32)] + self._labels + self._glabels)).astype(np.int32)),
         }
+
+
+_SUMMARY_KEYS = ("map", "map_50", "map_75", "map_small", "map_medium", "map_large",
+                 "mar_1", "mar_10", "mar_100", "mar_small", "mar_medium", "mar_large")
+MAX_DET_LIMIT, MAX_GT_LIMIT, MAX_CLASSES = 1024, 2048, 4096
+
+
+class CocoEvaluator:
+    """COCO AP (the summary of ``MeanAveragePrecision``'s COCO mode) without leaving the device.
+
+    ``update(detections, gt_boxes, gt_labels, gt_counts)`` takes ``yms.ops.detect``'s
+    :class:`~yms.ops.Detections` (or a (boxes [B, max_det, 4], scores [B, max_det], labels [B, max_det],
+    counts [B]) tuple) and padded device ground truths ([B, G, 4] fp32 xyxy, [B, G] int, [B] int; see
+    :meth:`pad_targets`), and matches them into epoch buffers of ``max_det`` rows per image: no host
+    synchronisation, no ``.cpu()``; the buffers double when they are full (decided from the shapes).
+    ``max_det`` is fixed by the first call; images are numbered in call order.  ``compute()`` runs the
+    device accumulation and reads the summary back once.  ``num_classes`` fixes the tables' class axis:
+    labels outside [0, num_classes) take no part."""
+
+    def __init__(self, num_classes, iou_thresholds=None, capacity_images=1024):
+        if not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"yms.metrics.CocoEvaluator takes 1 to {MAX_CLASSES} classes")
+        if iou_thresholds is None:
+            thr = np.linspace(.5, .95, int(np.round((.95 - .5) / .05)) + 1, endpoint=True)
+        else:
+            thr = np.asarray(list(iou_thresholds), dtype=np.float64).reshape(-1)
+        if not 1 <= thr.size <= MAX_THRESHOLDS:
+            raise ValueError(f"yms.metrics.CocoEvaluator takes 1 to {MAX_THRESHOLDS} iou_thresholds")
+        if not (np.all(thr > 0) and np.all(thr <= 1) and np.all(np.diff(thr) > 0)):
+            raise ValueError("iou_thresholds must be increasing values in (0, 1]")
+        if int(capacity_images) < 1:
+            raise ValueError("capacity_images must be at least 1")
+        self.num_classes = int(num_classes)
+        self.iou_thresholds = np.ascontiguousarray(thr)
+        self.capacity_images = int(capacity_images)
+        self._dev = None
+        self._buf = None             # (score, label, rank, matched [4, cap], ignored [4, cap])
+        self._cap = 0                # rows
+        self._order = None
+        self.reset()
+
+    def reset(self):
+        """Start a new epoch: the buffers and max_det stay, the counters are zeroed (on the device)."""
+        self._n_images = 0
+        if self._dev is not None:
+            self._npig.zero_()
+            self._gt_seen.zero_()
+        else:
+            self._max_det = None
+
+    def to(self, device):      # torchmetrics-style no-op (state lives where the first update's tensors do)
+        return self
+
+    @staticmethod
+    def pad_targets(targets, device):
+        """[{'boxes' [k, 4], 'labels' [k]}, ...] (numpy arrays or tensors) -> (gt_boxes [B, G, 4] fp32,
+        gt_labels [B, G] int32 padded with -1, gt_counts [B] int32) on ``device``, G = the largest k.
+        Host work and one upload (tensors already on a device are read back first)."""
+        host = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        bs = [host(t["boxes"]).astype(np.float32).reshape(-1, 4) for t in targets]
+        ls = [host(t["labels"]).astype(np.int32).reshape(-1) for t in targets]
+        B = len(targets)
+        G = max([len(l) for l in ls] + [0])
+        boxes = np.zeros((B, G, 4), np.float32)
+        labels = np.full((B, G), -1, np.int32)
+        counts = np.zeros(B, np.int32)
+        for i, (b, l) in enumerate(zip(bs, ls)):
+            if len(b) != len(l):
+                raise ValueError("a target's boxes and labels must have the same length")
+            boxes[i, :len(l)], labels[i, :len(l)], counts[i] = b, l, len(l)
+        packed = np.concatenate([boxes.view(np.int32).reshape(-1), labels.reshape(-1), counts])
+        d = torch.from_numpy(packed).to(device)
+        nb, nl = B * G * 4, B * G
+        return d[:nb].view(torch.float32).view(B, G, 4), d[nb:nb + nl].view(B, G), d[nb + nl:]
+
+    def _reserve(self, dev, rows):
+        """Epoch buffers for at least `rows` rows: doubled (from capacity_images) and copied on the device."""
+        if self._dev is None:
+            self._dev = dev
+            self._npig = torch.zeros((self.num_classes, N_AREAS), dtype=torch.int32, device=dev)
+            self._gt_seen = torch.zeros(self.num_classes, dtype=torch.int32, device=dev)
+        elif dev != self._dev:
+            raise ValueError("yms: CocoEvaluator.update got tensors on another device than its first call")
+        if rows <= self._cap:
+            return
+        cap = max(self._cap, self.capacity_images * self._max_det)
+        while cap < rows:
+            cap *= 2
+        new = (torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+               torch.empty(cap, dtype=torch.int32, device=dev), torch.empty((N_AREAS, cap), dtype=torch.int16, device=dev),
+               torch.empty((N_AREAS, cap), dtype=torch.int16, device=dev))
+        used = self._n_images * self._max_det
+        if self._buf is not None and used:
+            for o, n in zip(self._buf, new):
+                n[..., :used].copy_(o[..., :used])
+        self._buf, self._cap = new, cap
+
+    def update(self, detections, gt_boxes, gt_labels, gt_counts):
+        if isinstance(detections, (tuple, list)):
+            boxes, scores, labels, counts = detections
+        else:
+            boxes, scores, labels, counts = detections.boxes, detections.scores, detections.labels, detections.counts
+        for t in (boxes, scores, labels, counts, gt_boxes, gt_labels, gt_counts):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+                raise RuntimeError("yms: CocoEvaluator runs on ROCm GPU tensors only (no CPU fallback)")
+        if boxes.dim() != 3 or boxes.shape[2] != 4:
+            raise ValueError(f"yms: detections' boxes must be [B, max_det, 4], got {tuple(boxes.shape)}")
+        B, M = int(boxes.shape[0]), int(boxes.shape[1])
+        if tuple(scores.shape) != (B, M) or tuple(labels.shape) != (B, M) or tuple(counts.shape) != (B,):
+            raise ValueError("yms: detections' scores / labels must be [B, max_det] and counts [B]")
+        if gt_labels.dim() != 2 or gt_labels.shape[0] != B or tuple(gt_boxes.shape) != (B, gt_labels.shape[1], 4) \
+                or tuple(gt_counts.shape) != (B,):
+            raise ValueError("yms: ground truths must be padded to gt_boxes [B, G, 4], gt_labels [B, G], gt_counts [B]")
+        G = int(gt_labels.shape[1])
+        if self._max_det is None:
+            if not 1 <= M <= MAX_DET_LIMIT:
+                raise ValueError(f"yms: max_det must be in 1..{MAX_DET_LIMIT}")
+            self._max_det = M
+        elif M != self._max_det:
+            raise ValueError(f"yms: max_det is {self._max_det} since the first update, got {M}")
+        if B == 0:
+            return
+        dev = boxes.device
+        i32 = torch.int32
+        db = boxes.detach().to(torch.float32).contiguous()
+        ds = scores.detach().to(torch.float32).contiguous()
+        dl = labels.to(i32).contiguous()
+        dc = counts.to(i32).contiguous()
+        gb = gt_boxes.detach().to(torch.float32).contiguous()
+        gl = gt_labels.to(i32).contiguous()
+        gc = gt_counts.to(i32).contiguous()
+        row0 = self._n_images * M
+        self._reserve(dev, row0 + B * M)
+        if self._order is None or self._order.numel() < B * M:
+            self._order = torch.empty(B * M, dtype=i32, device=dev)
+        score, label, rank, matched, ignored = self._buf
+        thr = self.iou_thresholds
+        L.call("yms_map_match_coco_fixed", B, M, db.data_ptr(), ds.data_ptr(), dl.data_ptr(), dc.data_ptr(), G,
+               gb.data_ptr() if G else None, gl.data_ptr() if G else None, gc.data_ptr(), int(thr.size), _hp(thr),
+               self.num_classes, self._cap, row0, score.data_ptr(), label.data_ptr(), rank.data_ptr(),
+               matched.data_ptr(), ignored.data_ptr(), self._npig.data_ptr(), self._order.data_ptr(),
+               L.stream_ptr(dev))
+        if G:     # classes with a ground truth of any size, for `classes`
+            live = (torch.arange(G, device=dev).unsqueeze(0) < gc.unsqueeze(1)) & (gl >= 0) & (gl < self.num_classes)
+            self._gt_seen.scatter_add_(0, gl.clamp(0, self.num_classes - 1).reshape(-1).long(),
+                                       live.reshape(-1).to(i32))
+        self._n_images += B
+
+    def _tables_dev(self):
+        """The device accumulate -> (precision, recall) device tensors."""
+        T, K = int(self.iou_thresholds.size), self.num_classes
+        dev = self._dev if self._dev is not None else torch.device("cuda", torch.cuda.current_device())
+        if self._dev is None:
+            self._reserve(dev, 0)
+        n_rows = self._n_images * (self._max_det or 0)
+        precision = torch.empty((T, 101, K, N_AREAS, len(MAX_DETS)), dtype=torch.float64, device=dev)
+        recall = torch.empty((T, K, N_AREAS, len(MAX_DETS)), dtype=torch.float64, device=dev)
+        wsb = L.lib().yms_map_accumulate_coco_dev_ws_bytes(n_rows, T, K)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        buf = self._buf if n_rows else (None,) * 5
+        L.call("yms_map_accumulate_coco_dev", n_rows, self._cap, *[L.ptr(b) for b in buf], T, K,
+               self._npig.data_ptr(), precision.data_ptr(), recall.data_ptr(), ws.data_ptr(), wsb, L.stream_ptr(dev))
+        return precision, recall
+
+    def tables(self):
+        """COCOeval's ``eval['precision']`` [T, 101, K, 4, 3], ``eval['recall']`` [T, K, 4, 3] and the
+        per-(class, area) count of non-ignored ground truths, as numpy arrays."""
+        precision, recall = self._tables_dev()
+        return precision.cpu().numpy(), recall.cpu().numpy(), self._npig.cpu().numpy()
+
+    def compute(self):
+        precision, recall = self._tables_dev()
+        K, thr = self.num_classes, self.iou_thresholds
+        zero = torch.zeros((), dtype=torch.float64, device=precision.device)
+
+        def mean(s, dims):
+            m = s > -1
+            cnt = m.sum(dims)
+            return torch.where(cnt > 0, torch.where(m, s, zero).sum(dims) / cnt.clamp(min=1), zero - 1.0)
+
+        def ap(area=0, iou=None):
+            s = precision
+            if iou is not None:
+                s = s[np.nonzero(np.isclose(thr, iou))[0].tolist()]
+            return mean(s[:, :, :, area, 2], (0, 1, 2))
+
+        def ar(area=0, md=2):
+            return mean(recall[:, :, area, md], (0, 1))
+
+        n_rows = self._n_images * (self._max_det or 0)
+        det_seen = torch.zeros(K, dtype=torch.int32, device=precision.device)
+        if n_rows:
+            lab = self._buf[1][:n_rows]
+            det_seen.scatter_add_(0, lab.clamp(0, K - 1).long(), ((lab >= 0) & (lab < K)).to(torch.int32))
+        parts = [torch.stack([ap(), ap(iou=0.5), ap(iou=0.75), ap(1), ap(2), ap(3), ar(md=0), ar(md=1), ar(md=2),
+                              ar(1), ar(2), ar(3)]),
+                 mean(precision[:, :, :, 0, 2], (0, 1)), mean(recall[:, :, 0, 2], (0,)),
+                 self._npig[:, 0].to(torch.float64), (self._gt_seen + det_seen).to(torch.float64)]
+        host = torch.cat(parts).cpu().numpy()                        # the one host read
+        vals, ap_c, ar_c, with_gt, seen = np.split(host, [12, 12 + K, 12 + 2 * K, 12 + 3 * K])
+        out = {k: torch.tensor(float(v), dtype=torch.float64) for k, v in zip(_SUMMARY_KEYS, vals)}
+        classes = [c for c in range(K) if with_gt[c] > 0]
+        out["map_per_class"] = {c: float(ap_c[c]) for c in classes}
+        out["mar_100_per_class"] = {c: float(ar_c[c]) for c in classes}
+        out["classes"] = torch.tensor(np.nonzero(seen > 0)[0].astype(np.int32))
+        return out
