@@ -646,7 +646,7 @@ yms_status yms_optim_grad_norm(const void* table, long nchunks, const void* grad
  * EMA factor in fp64 from the device counters:
  *   SGD   d = g + wd p;  b' = d (first update) | mom b + d;  p' = p - lr (nesterov ? d + mom b' : b')
  *   Adam  d = g + wd p;  m' = b1 m + (1-b1) d;  v' = b2 v + (1-b2) d^2;
- *         p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps),  bc_i = 1 - b_i^t   (no amsgrad, not AdamW)
+ *         p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps),  bc_i = 1 - b_i^t   (no amsgrad; AdamW: below)
  *   EMA   e' = delta e + (1 - delta) p'
  * partials != NULL (npartials of yms_optim_grad_norm's sums): every block re-reduces them in one
  * fixed order, scales g by min(1, max_norm / (norm + 1e-6)) (torch's clip_grad_norm_) and, when the
@@ -654,6 +654,46 @@ yms_status yms_optim_grad_norm(const void* table, long nchunks, const void* grad
 yms_status yms_optim_step(int kind, const void* table, long nchunks, const void* grad_base,
                           const yms_optim_hyper* hyper, yms_optim_counters* counters, const float* partials,
                           int npartials, void* stream);
+/* The same step with a third update kind, a second EMA rule and a schedule evaluated on the device.
+ * yms_optim_step is this call with ext = sched_out = NULL (bit-identical) and kinds 0 / 1 only.
+ *   AdamW (kind 2)  d = g clip (no wd p term);  p1 = p * (float)(1 - lr wd), the factor formed in fp64;
+ *         m', v' as Adam's from d;  p' = p1 - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps)
+ *         (torch.optim.AdamW without amsgrad; the hyper row is Adam's).
+ * ext (a DEVICE record like hyper, may be NULL = today's EMA rule, no schedule):
+ *   ema_rule YMS_OPTIM_EMA_EXPMOM: mu = (1 - m) exp(-(k + 1) / gamma) + m at ema_step k (gamma <= 0:
+ *         mu = m), e' = (1 - mu) e + mu p', with m = hyper->ema_decay and gamma = hyper->ema_tau.
+ *   seg[0 .. nsegments): the schedule.  Its index is n = counters->step + counters->skipped, the
+ *         number of calls before this one (a skipped step advances it).  Segment s is the factor
+ *         from (n <= begin), to (n >= end), else with u = (n - begin) / (end - begin)
+ *         linear from + (to - from) u | cosine to + (from - to)(1 + cos(pi u)) / 2.  Group g runs at
+ *         group[g][0] times the product of the factors of the YMS_OPTIM_SCHED_LR segments whose
+ *         `groups` has bit g, and at group[g][1] (SGD momentum / Adam beta1, whose 1 - beta1 and bias
+ *         correction follow it) times that of the YMS_OPTIM_SCHED_MOMENTUM ones: fp64, before the
+ *         casts to float.  The record is never read by the host: nsegments is clamped to
+ *         [0, YMS_OPTIM_MAX_SEGMENTS] and a segment with end <= begin or an unknown target or shape
+ *         is ignored, by the kernel.
+ * sched_out (device, [YMS_OPTIM_MAX_GROUPS][2], may be NULL): the tick stores { lr, momentum | beta1 }
+ * as this call used them, for logging without a sync.  Launch count as yms_optim_step. */
+#define YMS_OPTIM_ADAMW 2
+#define YMS_OPTIM_EMA_TAU 0
+#define YMS_OPTIM_EMA_EXPMOM 1
+#define YMS_OPTIM_SCHED_LR 0
+#define YMS_OPTIM_SCHED_MOMENTUM 1
+#define YMS_OPTIM_SCHED_LINEAR 0
+#define YMS_OPTIM_SCHED_COSINE 1
+#define YMS_OPTIM_MAX_SEGMENTS 8
+typedef struct {
+  double begin, end, from, to;
+  int target, shape, groups, pad;   /* groups: bit g = group g */
+} yms_optim_segment;
+typedef struct {
+  double ema_rule;
+  double nsegments;
+  yms_optim_segment seg[YMS_OPTIM_MAX_SEGMENTS];
+} yms_optim_ext;
+yms_status yms_optim_step_ext(int kind, const void* table, long nchunks, const void* grad_base,
+                              const yms_optim_hyper* hyper, const yms_optim_ext* ext, yms_optim_counters* counters,
+                              double* sched_out, const float* partials, int npartials, void* stream);
 /* Exchange every YMS_OPTIM_EMA row's tensor with its EMA slot, in place, in one launch. */
 yms_status yms_optim_swap(const void* table, long nchunks, void* stream);
 

@@ -1,5 +1,6 @@
-// Optimizer step for the flat-arena training loop: SGD / Adam, weight EMA, gradient-norm clipping and
-// the device-side non-finite skip, in a launch count that does not depend on the number of tensors.
+// Optimizer step for the flat-arena training loop: SGD / Adam / AdamW, weight EMA (two rules), gradient-norm
+// clipping, the device-side non-finite skip and a piecewise schedule of the learning rate and momentum
+// evaluated on the device, in a launch count that does not depend on the number of tensors.
 //
 // The tensors are rows of a device table (yms_optim_chunk, include/yms.h): every row is at most CHUNK
 // consecutive elements of ONE tensor and one block takes one row, so a block's work is the same
@@ -55,7 +56,7 @@ __device__ __forceinline__ float norm_from_partials(const float* partials, int n
 
 struct StepCoef {
   float clip;          // gradient scale (1 without clipping)
-  float wd;
+  float wd;            // AdamW: the decay factor 1 - lr wd
   float a, oma;        // SGD: momentum, -        Adam: beta1, 1 - beta1
   float b, omb;        // SGD: lr, -              Adam: beta2, 1 - beta2
   float step, bc2s;    // Adam: lr / bc1, sqrt(bc2)
@@ -64,9 +65,43 @@ struct StepCoef {
   int first, nesterov;
 };
 
+// The schedule (include/yms.h): the products of the factors that the segments holding group g
+// contribute at index n, for the learning rate and for the momentum.  One lane, fp64.
+__device__ __forceinline__ void sched_factors(const yms_optim_ext* ext, int g, double n, double& flr, double& fmom) {
+  flr = 1.0;
+  fmom = 1.0;
+  const double ns = ext->nsegments;
+  const int nseg = ns >= (double)YMS_OPTIM_MAX_SEGMENTS ? YMS_OPTIM_MAX_SEGMENTS : (ns >= 1.0 ? (int)ns : 0);   // nan: 0
+  for (int s = 0; s < nseg; ++s) {
+    const yms_optim_segment sg = ext->seg[s];
+    const bool lr = sg.target == YMS_OPTIM_SCHED_LR;
+    if (!(sg.end > sg.begin) || !((sg.groups >> g) & 1) || (!lr && sg.target != YMS_OPTIM_SCHED_MOMENTUM) ||
+        (sg.shape != YMS_OPTIM_SCHED_LINEAR && sg.shape != YMS_OPTIM_SCHED_COSINE))
+      continue;
+    double f;
+    if (n <= sg.begin) {
+      f = sg.from;
+    } else if (n >= sg.end) {
+      f = sg.to;
+    } else {
+      const double u = (n - sg.begin) / (sg.end - sg.begin);
+      f = sg.shape == YMS_OPTIM_SCHED_LINEAR ? sg.from + (sg.to - sg.from) * u
+                                             : sg.to + (sg.from - sg.to) * (1.0 + cospi(u)) / 2.0;
+      // (cospi, not cos(pi u): no large-argument reduction, which cost Adam's update a wave per SIMD)
+    }
+    if (lr) flr *= f; else fmom *= f;
+  }
+}
+
 template <int KIND>
 __device__ __forceinline__ void update1(const StepCoef& k, float g, float& p, float& s0, float& s1) {
-  const float d = g * k.clip + k.wd * p;
+  float d;
+  if (KIND == YMS_OPTIM_ADAMW) {
+    p = p * k.wd;
+    d = g * k.clip;
+  } else {
+    d = g * k.clip + k.wd * p;
+  }
   if (KIND == YMS_OPTIM_SGD) {
     const float b = k.first ? d : k.a * s0 + d;
     s0 = b;
@@ -81,10 +116,12 @@ __device__ __forceinline__ void update1(const StepCoef& k, float g, float& p, fl
   }
 }
 
-template <int KIND>
+// EXT: an extension record is given.  Without one the kernel is the code it was before the record
+// existed (the schedule and the second EMA rule are compiled out), so yms_optim_step's cost is too.
+template <int KIND, bool EXT>
 __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_chunk* __restrict__ table,
                                                                 const char* gbase, const yms_optim_hyper* hy,
-                                                                const yms_optim_counters* cnt,
+                                                                const yms_optim_ext* ext, const yms_optim_counters* cnt,
                                                                 const float* partials, int np) {
   __shared__ double red[4];
   __shared__ StepCoef shk;
@@ -94,7 +131,7 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_c
   const bool ema = (c.flags & YMS_OPTIM_EMA) && c.e;
   if (!upd && !ema) return;
   const float* g = upd ? grad_ptr(c, gbase) : nullptr;
-  float* s1 = KIND == YMS_OPTIM_ADAM ? c.s1 : nullptr;
+  float* s1 = KIND != YMS_OPTIM_SGD ? c.s1 : nullptr;
 
   // a full row with aligned tensors: every load goes out before the prologue
   const bool wide = c.n == OPT_CHUNK && al16(c.p) && (!upd || (al16(c.s0) && al16(s1))) && (!ema || al16(c.e));
@@ -113,7 +150,7 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_c
           for (int q = 0; q < 4; ++q) G[j][q] = g[i + q];
         }
         S0[j] = *reinterpret_cast<const f32x4*>(c.s0 + i);
-        if (KIND == YMS_OPTIM_ADAM) S1[j] = *reinterpret_cast<const f32x4*>(s1 + i);
+        if (KIND != YMS_OPTIM_SGD) S1[j] = *reinterpret_cast<const f32x4*>(s1 + i);
       }
       if (ema) E[j] = *reinterpret_cast<const f32x4*>(c.e + i);
     }
@@ -127,13 +164,20 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_c
   if (tid == 0) {
     StepCoef k;
     const double* h = hy->group[c.group];
-    const double lr = h[0], b1 = h[1], b2 = h[2];
+    double lr = h[0], b1 = h[1];
+    const double b2 = h[2];
+    if (EXT) {
+      double flr, fmom;
+      sched_factors(ext, c.group, (double)cnt->step + (double)cnt->skipped, flr, fmom);
+      lr *= flr;
+      b1 *= fmom;
+    }
     k.clip = 1.0f;
     if (partials && hy->max_norm > 0.0) {
       const float c0 = (float)hy->max_norm / (norm + 1e-6f);
       k.clip = c0 > 1.0f ? 1.0f : c0;        // a nan norm passes through, as torch.clamp does
     }
-    k.wd = (float)h[4];
+    k.wd = KIND == YMS_OPTIM_ADAMW ? (float)(1.0 - lr * h[4]) : (float)h[4];
     k.eps = (float)h[3];
     k.nesterov = h[5] != 0.0;
     k.first = cnt->step == 0;
@@ -147,9 +191,16 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_c
       k.bc2s = (float)sqrt(bc2);
     }
     double dl = hy->ema_decay;
-    if (hy->ema_tau > 0.0) dl *= 1.0 - exp(-((double)cnt->ema_step + 1.0) / hy->ema_tau);
-    k.ed = (float)dl;
-    k.eomd = (float)(1.0 - dl);
+    if (EXT && ext->ema_rule == (double)YMS_OPTIM_EMA_EXPMOM) {
+      // dl is the momentum floor m here; the EMA keeps 1 - mu of itself
+      if (hy->ema_tau > 0.0) dl += (1.0 - dl) * exp(-((double)cnt->ema_step + 1.0) / hy->ema_tau);
+      k.ed = (float)(1.0 - dl);
+      k.eomd = (float)dl;
+    } else {
+      if (hy->ema_tau > 0.0) dl *= 1.0 - exp(-((double)cnt->ema_step + 1.0) / hy->ema_tau);
+      k.ed = (float)dl;
+      k.eomd = (float)(1.0 - dl);
+    }
     shk = k;
   }
   lds_barrier();
@@ -162,13 +213,13 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_c
       if (upd) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float p = P[j][q], a = S0[j][q], b = KIND == YMS_OPTIM_ADAM ? S1[j][q] : 0.0f;
+          float p = P[j][q], a = S0[j][q], b = KIND != YMS_OPTIM_SGD ? S1[j][q] : 0.0f;
           update1<KIND>(k, G[j][q], p, a, b);
           P[j][q] = p; S0[j][q] = a; S1[j][q] = b;
         }
         *reinterpret_cast<f32x4*>(c.p + i) = P[j];
         *reinterpret_cast<f32x4*>(c.s0 + i) = S0[j];
-        if (KIND == YMS_OPTIM_ADAM) *reinterpret_cast<f32x4*>(s1 + i) = S1[j];
+        if (KIND != YMS_OPTIM_SGD) *reinterpret_cast<f32x4*>(s1 + i) = S1[j];
       }
       if (ema) {
 #pragma unroll
@@ -182,20 +233,30 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_step_kernel(const yms_optim_c
   for (int i = tid; i < c.n; i += OPT_BLOCK) {
     float p = c.p[i];
     if (upd) {
-      float a = c.s0[i], b = KIND == YMS_OPTIM_ADAM ? s1[i] : 0.0f;
+      float a = c.s0[i], b = KIND != YMS_OPTIM_SGD ? s1[i] : 0.0f;
       update1<KIND>(k, g[i], p, a, b);
       c.p[i] = p;
       c.s0[i] = a;
-      if (KIND == YMS_OPTIM_ADAM) s1[i] = b;
+      if (KIND != YMS_OPTIM_SGD) s1[i] = b;
     }
     if (ema) c.e[i] = k.ed * c.e[i] + k.eomd * p;
   }
 }
 
 // After the update (stream order): advance the counters.  One block; lane 0 writes.
-__global__ __launch_bounds__(OPT_BLOCK) void optim_tick_kernel(const yms_optim_hyper* hy, yms_optim_counters* cnt,
+// With sched_out, lanes 0 .. 15 first store the learning rate and momentum this call ran at, one
+// (group, target) each, from the counters as the update read them.
+__global__ __launch_bounds__(OPT_BLOCK) void optim_tick_kernel(const yms_optim_hyper* hy, const yms_optim_ext* ext,
+                                                                yms_optim_counters* cnt, double* sched_out,
                                                                 const float* partials, int np) {
   __shared__ double red[4];
+  const int step0 = cnt->step, skipped0 = cnt->skipped;
+  if (sched_out && threadIdx.x < 2 * YMS_OPTIM_MAX_GROUPS) {
+    const int g = threadIdx.x >> 1, which = threadIdx.x & 1;
+    double f[2] = {1.0, 1.0};
+    if (ext) sched_factors(ext, g, (double)step0 + (double)skipped0, f[0], f[1]);
+    sched_out[threadIdx.x] = hy->group[g][which] * (which ? f[1] : f[0]);
+  }
   float norm = 0.0f;
   bool skip = false;
   if (partials) {
@@ -204,9 +265,9 @@ __global__ __launch_bounds__(OPT_BLOCK) void optim_tick_kernel(const yms_optim_h
   }
   if (threadIdx.x == 0) {
     if (skip) {
-      cnt->skipped = cnt->skipped + 1;
+      cnt->skipped = skipped0 + 1;
     } else {
-      cnt->step = cnt->step + 1;
+      cnt->step = step0 + 1;
       cnt->ema_step = cnt->ema_step + 1;
     }
     if (partials) cnt->grad_norm = norm;
@@ -304,6 +365,18 @@ long table_chunks(int njobs, const yms_optim_job* jobs) {
   return n;
 }
 
+template <int KIND>
+void launch_step(bool ext, unsigned grid, hipStream_t st, const yms_optim_chunk* t, const char* gb,
+                 const yms_optim_hyper* hy, const yms_optim_ext* ex, const yms_optim_counters* cnt, const float* partials,
+                 int np) {
+  if (ext)
+    hipLaunchKernelGGL((optim_step_kernel<KIND, true>), dim3(grid), dim3(OPT_BLOCK), 0, st, t, gb, hy, ex, cnt, partials,
+                       np);
+  else
+    hipLaunchKernelGGL((optim_step_kernel<KIND, false>), dim3(grid), dim3(OPT_BLOCK), 0, st, t, gb, hy, ex, cnt,
+                       partials, np);
+}
+
 }  // namespace
 }  // namespace yms
 
@@ -365,24 +438,34 @@ yms_status yms_optim_grad_norm(const void* table, long nchunks, const void* grad
   return launch_status();
 }
 
-yms_status yms_optim_step(int kind, const void* table, long nchunks, const void* grad_base,
-                          const yms_optim_hyper* hyper, yms_optim_counters* counters, const float* partials,
-                          int npartials, void* stream) {
-  if ((kind != YMS_OPTIM_SGD && kind != YMS_OPTIM_ADAM) || !table || nchunks <= 0 || nchunks > 0x7fffffffL ||
-      !hyper || !counters || npartials < 0 || (partials != nullptr) != (npartials > 0))
+yms_status yms_optim_step_ext(int kind, const void* table, long nchunks, const void* grad_base,
+                              const yms_optim_hyper* hyper, const yms_optim_ext* ext, yms_optim_counters* counters,
+                              double* sched_out, const float* partials, int npartials, void* stream) {
+  if ((kind != YMS_OPTIM_SGD && kind != YMS_OPTIM_ADAM && kind != YMS_OPTIM_ADAMW) || !table || nchunks <= 0 ||
+      nchunks > 0x7fffffffL || !hyper || !counters || npartials < 0 || (partials != nullptr) != (npartials > 0))
     return YMS_ERR_INVALID;
   if (npartials > OPT_MAX_PARTIALS) return YMS_ERR_UNSUPPORTED;
   const yms_optim_chunk* t = static_cast<const yms_optim_chunk*>(table);
   const char* gb = static_cast<const char*>(grad_base);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)nchunks;
   if (kind == YMS_OPTIM_SGD)
-    hipLaunchKernelGGL(optim_step_kernel<YMS_OPTIM_SGD>, dim3((unsigned)nchunks), dim3(OPT_BLOCK), 0,
-                       (hipStream_t)stream, t, gb, hyper, counters, partials, npartials);
+    launch_step<YMS_OPTIM_SGD>(ext != nullptr, grid, st, t, gb, hyper, ext, counters, partials, npartials);
+  else if (kind == YMS_OPTIM_ADAM)
+    launch_step<YMS_OPTIM_ADAM>(ext != nullptr, grid, st, t, gb, hyper, ext, counters, partials, npartials);
   else
-    hipLaunchKernelGGL(optim_step_kernel<YMS_OPTIM_ADAM>, dim3((unsigned)nchunks), dim3(OPT_BLOCK), 0,
-                       (hipStream_t)stream, t, gb, hyper, counters, partials, npartials);
-  hipLaunchKernelGGL(optim_tick_kernel, dim3(1), dim3(OPT_BLOCK), 0, (hipStream_t)stream, hyper, counters, partials,
+    launch_step<YMS_OPTIM_ADAMW>(ext != nullptr, grid, st, t, gb, hyper, ext, counters, partials, npartials);
+  hipLaunchKernelGGL(optim_tick_kernel, dim3(1), dim3(OPT_BLOCK), 0, st, hyper, ext, counters, sched_out, partials,
                      npartials);
   return launch_status();
+}
+
+yms_status yms_optim_step(int kind, const void* table, long nchunks, const void* grad_base,
+                          const yms_optim_hyper* hyper, yms_optim_counters* counters, const float* partials,
+                          int npartials, void* stream) {
+  if (kind != YMS_OPTIM_SGD && kind != YMS_OPTIM_ADAM) return YMS_ERR_INVALID;
+  return yms_optim_step_ext(kind, table, nchunks, grad_base, hyper, nullptr, counters, nullptr, partials, npartials,
+                            stream);
 }
 
 yms_status yms_optim_swap(const void* table, long nchunks, void* stream) {

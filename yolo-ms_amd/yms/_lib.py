@@ -80,9 +80,13 @@ class BnBwdFinalizeJob(ctypes.Structure):
 
 
 # optimizer records (include/yms.h, "optimizer step")
-OPTIM_SGD, OPTIM_ADAM = 0, 1
+OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
 OPTIM_GRAD_NONE, OPTIM_GRAD_ABS, OPTIM_EMA = 1, 2, 4
 OPTIM_MAX_GROUPS = 8
+OPTIM_EMA_TAU, OPTIM_EMA_EXPMOM = 0, 1
+OPTIM_SCHED_LR, OPTIM_SCHED_MOMENTUM = 0, 1
+OPTIM_SCHED_LINEAR, OPTIM_SCHED_COSINE = 0, 1
+OPTIM_MAX_SEGMENTS = 8
 
 
 class OptimJob(ctypes.Structure):
@@ -99,6 +103,16 @@ class OptimChunk(ctypes.Structure):
 class OptimHyper(ctypes.Structure):
     _fields_ = [(k, ctypes.c_double) for k in ("max_norm", "skip_nonfinite", "ema_decay", "ema_tau")] + [
         ("group", ctypes.c_double * 8 * OPTIM_MAX_GROUPS)]
+
+
+class OptimSegment(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("begin", "end", "start", "stop")] + [
+        (k, ctypes.c_int) for k in ("target", "shape", "groups", "pad")]
+
+
+class OptimExt(ctypes.Structure):
+    _fields_ = [("ema_rule", ctypes.c_double), ("nsegments", ctypes.c_double),
+                ("seg", OptimSegment * OPTIM_MAX_SEGMENTS)]
 
 
 _L = ctypes.c_long
@@ -212,6 +226,7 @@ _SIGS = {
     "yms_optim_norm_partials": (_I, [_L]),
     "yms_optim_grad_norm": (_I, [_P, _L, _P, _P, _P]),
     "yms_optim_step": (_I, [_I, _P, _L, _P, _P, _P, _P, _I, _P]),
+    "yms_optim_step_ext": (_I, [_I, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P]),
     "yms_optim_swap": (_I, [_P, _L, _P]),
 }
 

@@ -1,21 +1,31 @@
-"""Optimizer step on the package's own kernels (csrc/optim.hip): SGD / Adam, weight EMA, gradient-norm
-clipping and a device-side non-finite skip, in two launches per step (three with clip or skip) whatever
-the number of tensors, with no host sync and no per-step upload.
+"""Optimizer step on the package's own kernels (csrc/optim.hip): SGD / Adam / AdamW, weight EMA,
+gradient-norm clipping, a device-side non-finite skip and a per-iteration schedule evaluated on the
+device, in two launches per step (three with clip or skip) whatever the number of tensors, with no host
+sync and no per-step upload.
 
     opt = yms.optim.build_optimizer(model, cfg)        # for tools/utils.py:11-25 get_optimizer(model.parameters(), cfg)
     opt = yms.optim.SGD(model.parameters(), lr=0.01, momentum=0.937, nesterov=True, weight_decay=5e-4,
                         clip_grad_norm=10.0, skip_nonfinite=True)
     opt.attach_ema(model)                              # ModelEMA(decay=0.9999, tau=2000)
+    opt.set_schedule([Segment(0, 1000, 1e-5, 1.0),     # linear warm-up, then a cosine to 5 %: no upload per step,
+                      Segment(45000, 90000, 1.0, 0.05, shape="cosine")])   # and a captured step follows it
     ...
     loss.backward(); opt.step()
     with opt.ema_applied():
         validate(model)
+    opt = yms.optim.yolo_ms_recipe(model, iters_per_epoch)   # AdamW + exp-momentum EMA + warm-up / cosine
 
-Both classes are ``torch.optim.Optimizer`` subclasses: ``param_groups``, ``zero_grad``, the torch LR
+The classes are ``torch.optim.Optimizer`` subclasses: ``param_groups``, ``zero_grad``, the torch LR
 schedulers and ``yms.checkpoint`` work unchanged, and ``state_dict()`` is torch's format (a checkpoint
-of ``torch.optim.SGD`` / ``Adam`` loads here and the reverse).  One divergence: Adam's ``'step'`` is a
-single optimizer-wide device count (torch counts per parameter), so every ``'step'`` of a loaded state
-must agree, and a parameter frozen for some steps reports the common count.
+of ``torch.optim.SGD`` / ``Adam`` / ``AdamW`` loads here and the reverse).  One divergence: Adam's and
+AdamW's ``'step'`` is a single optimizer-wide device count (torch counts per parameter), so every
+``'step'`` of a loaded state must agree, and a parameter frozen for some steps reports the common count.
+
+A torch scheduler changes ``param_groups`` every iteration, which costs an upload per step and cannot
+reach a captured step without a host call.  ``set_schedule`` instead puts up to 8 ``Segment`` s on the
+device once; every step multiplies each group's learning rate (or momentum / beta1) by the segments'
+factors at the schedule index, the number of ``step()`` calls so far (updates + skipped steps), which the
+kernel reads from its own counters.  ``schedule_factor`` is the same formula on the host.
 
 The tensors reach the kernel as a cached device table of fixed-size chunks (``yms_optim_table_build``).
 When every gradient is a view of one storage -- the backward's flat arena (runner.py) -- the table
@@ -32,18 +42,61 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-from collections import OrderedDict
+import math
+from collections import OrderedDict, namedtuple
 
 import torch
 from torch.optim import Optimizer
 
 from . import _lib as L
 
-__all__ = ["SGD", "Adam", "build_optimizer", "optimizer_config"]
+__all__ = ["SGD", "Adam", "AdamW", "Segment", "schedule_factor", "build_optimizer", "optimizer_config",
+           "yolo_ms_recipe"]
 
 _TABLES_MAX = 4
 _HYPER_DOUBLES = ctypes.sizeof(L.OptimHyper) // 8
 _STAGING_SLOTS = 4
+_TARGETS = {"lr": L.OPTIM_SCHED_LR, "momentum": L.OPTIM_SCHED_MOMENTUM}
+_SHAPES = {"linear": L.OPTIM_SCHED_LINEAR, "cosine": L.OPTIM_SCHED_COSINE}
+_EMA_RULES = {"tau": L.OPTIM_EMA_TAU, "exp_momentum": L.OPTIM_EMA_EXPMOM}
+
+Segment = namedtuple("Segment", "begin end start stop target shape groups", defaults=("lr", "linear", None))
+Segment.__doc__ = """One piece of a schedule: a FACTOR on the groups' base value of `target` ("lr", or "momentum" =
+SGD momentum / Adam beta1) that is `start` up to iteration `begin`, `stop` from iteration `end` on, and
+moves between them on a "linear" or half-"cosine" `shape` inside.  `groups`: the parameter-group indices
+it applies to (None = all).  Several segments on one target multiply.  A segment with end <= begin is
+ignored."""
+
+
+def _check_segment(s, ngroups=L.OPTIM_MAX_GROUPS):
+    if s.target not in _TARGETS or s.shape not in _SHAPES:
+        raise ValueError(f"yms.optim: a segment's target is one of {sorted(_TARGETS)} and its shape one of "
+                         f"{sorted(_SHAPES)}, got {s.target!r} / {s.shape!r}")
+    if s.groups is not None and not all(isinstance(g, int) and 0 <= g < ngroups for g in s.groups):
+        raise ValueError(f"yms.optim: a segment's groups are indices below {ngroups}, got {s.groups!r}")
+
+
+def schedule_factor(segments, n, group=0, target="lr"):
+    """The factor on `group`'s base `target` at schedule index `n` (the number of ``step()`` calls made
+    before): the product over the matching segments of  start (n <= begin) | stop (n >= end) | with
+    u = (n - begin) / (end - begin):  start + (stop - start) u  (linear),
+    stop + (start - stop)(1 + cos(pi u)) / 2  (cosine).  The kernel evaluates the same in fp64."""
+    f = 1.0
+    for s in segments or ():
+        s = Segment(*s)
+        _check_segment(s)
+        if not s.end > s.begin or s.target != target or (s.groups is not None and group not in s.groups):
+            continue
+        if n <= s.begin:
+            v = float(s.start)
+        elif n >= s.end:
+            v = float(s.stop)
+        else:
+            u = (n - s.begin) / (s.end - s.begin)
+            v = s.start + (s.stop - s.start) * u if s.shape == "linear" else \
+                s.stop + (s.start - s.stop) * (1.0 + math.cos(math.pi * u)) / 2.0
+        f *= v
+    return f
 
 
 def _round4(n):
@@ -63,7 +116,7 @@ class _Fused(Optimizer):
     _STATE_KEYS = ()
     _UNSUPPORTED = ()
 
-    def __init__(self, params, defaults, clip_grad_norm, skip_nonfinite):
+    def __init__(self, params, defaults, clip_grad_norm, skip_nonfinite, schedule=None):
         if clip_grad_norm is not None and not float(clip_grad_norm) > 0.0:
             raise ValueError(f"yms.optim: clip_grad_norm must be positive, got {clip_grad_norm}")
         self._built = False
@@ -94,7 +147,13 @@ class _Fused(Optimizer):
         self._tables = {}
         self.table_builds = 0                # table cache misses (tests)
         self.last_launches = 0
+        # yms_optim_ext (EMA rule + schedule) and the tick's read-out: fixed addresses, so a captured step keeps them
+        self._ext = torch.zeros(ctypes.sizeof(L.OptimExt), dtype=torch.uint8, device=dev)
+        self._sched = torch.zeros(L.OPTIM_MAX_GROUPS, 2, dtype=torch.float64, device=dev)
+        self._segments = ()
         self._built = True
+        if schedule is not None:
+            self.set_schedule(schedule)
 
     # ---- construction ---------------------------------------------------------------------
     def add_param_group(self, param_group):
@@ -137,8 +196,10 @@ class _Fused(Optimizer):
 
     def _hyper_values(self):
         ema = self._ema
+        exp = ema is not None and ema["rule"] == "exp_momentum"       # its two numbers ride in the decay / tau slots
         v = [self.clip_grad_norm or 0.0, 1.0 if self.skip_nonfinite else 0.0,
-             ema["decay"] if ema else 0.0, ema["tau"] if ema else 0.0]
+             (ema["momentum"] if exp else ema["decay"]) if ema else 0.0,
+             (ema["gamma"] if exp else ema["tau"]) if ema else 0.0]
         for g in self.param_groups:
             row = [float(x) for x in self._hyper_row(g)]
             v += row + [0.0] * (8 - len(row))
@@ -164,6 +225,52 @@ class _Fused(Optimizer):
         slot[1] = torch.cuda.Event()
         slot[1].record(torch.cuda.current_stream(self._dev))
         self._hyper_last = vals
+
+    # ---- the schedule and the EMA rule (yms_optim_ext) ---------------------------------------------
+    def set_schedule(self, segments):
+        """Put a schedule of up to 8 ``Segment`` s on the device (None or empty: remove it).  One
+        upload, here; no step uploads anything for it, and a step captured after this call follows it
+        through its replays.  The schedule is configuration, not state: its position is the saved
+        ``step`` + ``skipped`` counts, the segments come from the code that builds the optimizer."""
+        segs = tuple(Segment(*s) for s in (segments or ()))
+        if len(segs) > L.OPTIM_MAX_SEGMENTS:
+            raise ValueError(f"yms.optim: at most {L.OPTIM_MAX_SEGMENTS} schedule segments, got {len(segs)}")
+        for s in segs:
+            _check_segment(s, len(self.param_groups))
+        old, self._segments = self._segments, segs
+        try:
+            self._upload_ext()
+        except RuntimeError:
+            self._segments = old
+            raise
+
+    def _ema_rule(self):
+        return self._ema["rule"] if self._ema else "tau"
+
+    def _upload_ext(self):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("yms.optim: the schedule and the EMA rule are uploaded when they are set, which cannot "
+                               "be captured; call set_schedule() / attach_ema() before capturing")
+        ext = L.OptimExt(float(_EMA_RULES[self._ema_rule()]), float(len(self._segments)))
+        for i, s in enumerate(self._segments):
+            mask = (1 << L.OPTIM_MAX_GROUPS) - 1 if s.groups is None else sum(1 << g for g in set(s.groups))
+            ext.seg[i] = L.OptimSegment(float(s.begin), float(s.end), float(s.start), float(s.stop),
+                                        _TARGETS[s.target], _SHAPES[s.shape], mask, 0)
+        self._ext.copy_(torch.frombuffer(bytearray(bytes(ext)), dtype=torch.uint8))
+
+    def _use_ext(self):
+        """The new entry point serves AdamW, the second EMA rule and schedules; everything else keeps
+        calling yms_optim_step."""
+        return self._KIND == L.OPTIM_ADAMW or bool(self._segments) or self._ema_rule() != "tau"
+
+    @property
+    def scheduled(self):
+        """float64 [groups, 2] on the device: the learning rate and momentum (beta1) the last ``step()``
+        ran at, written by its tick (no sync).  Only steps of an AdamW, a scheduled or an exp-momentum-EMA
+        optimizer write it; for any other the values are ``param_groups``'."""
+        if not self._use_ext():
+            raise RuntimeError("yms.optim: no schedule is set; the step runs at the values in param_groups")
+        return self._sched[:len(self.param_groups)]
 
     # ---- the device table ---------------------------------------------------------------------
     def _build_table(self, goffs, absolute):
@@ -285,18 +392,31 @@ class _Fused(Optimizer):
             L.call("yms_optim_grad_norm", table.data_ptr(), nchunks, base, partials.data_ptr(), st)
             pp, npart = partials.data_ptr(), partials.numel()
             self.last_launches += 1
-        L.call("yms_optim_step", self._KIND, table.data_ptr(), nchunks, base, self._hyper.data_ptr(),
-               self._counters.data_ptr(), pp, npart, st)
+        if self._use_ext():
+            ext = self._ext.data_ptr() if self._segments or self._ema_rule() != "tau" else None
+            L.call("yms_optim_step_ext", self._KIND, table.data_ptr(), nchunks, base, self._hyper.data_ptr(), ext,
+                   self._counters.data_ptr(), self._sched.data_ptr(), pp, npart, st)
+        else:
+            L.call("yms_optim_step", self._KIND, table.data_ptr(), nchunks, base, self._hyper.data_ptr(),
+                   self._counters.data_ptr(), pp, npart, st)
         self.last_launches += 2              # the update and the counter tick
         torch.autograd.graph.increment_version(written)
         return loss
 
     # ---- EMA --------------------------------------------------------------------------------------
-    def attach_ema(self, model, decay=0.9999, tau=2000):
-        """Keep an exponential moving average of ``model``'s parameters and floating-point buffers (the
-        YOLOv5 / ultralytics ModelEMA rule: delta = decay * (1 - exp(-k / tau)) at the k-th update),
+    def attach_ema(self, model, decay=0.9999, tau=2000, *, rule="tau", momentum=0.0002, gamma=2000):
+        """Keep an exponential moving average of ``model``'s parameters and floating-point buffers,
         seeded from their current values and updated inside ``step()``.  The BN running statistics are
-        written by the forward; their EMA follows them at each optimizer step."""
+        written by the forward; their EMA follows them at each optimizer step.  At the k-th update:
+        rule "tau" (YOLOv5 / ultralytics ModelEMA): e' = delta e + (1 - delta) p', delta = decay (1 - exp(-k / tau));
+        rule "exp_momentum" (the RTMDet lineage's ExpMomentumEMA): e' = (1 - mu) e + mu p',
+        mu = (1 - momentum) exp(-k / gamma) + momentum."""
+        if rule not in _EMA_RULES:
+            raise ValueError(f"yms.optim: the EMA rule is one of {sorted(_EMA_RULES)}, got {rule!r}")
+        if rule == "exp_momentum" and not (0.0 <= momentum <= 1.0 and gamma > 0):
+            raise ValueError(f"yms.optim: exp_momentum needs 0 <= momentum <= 1 and gamma > 0, got {momentum}, {gamma}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("yms.optim: attach_ema() uploads and cannot be captured")
         from .checkpoint import _unwrap
         model = _unwrap(model)
         pidx = {id(p): i for i, p in enumerate(self._params)}
@@ -312,9 +432,11 @@ class _Fused(Optimizer):
                 extra.append((t, off))
             off += _round4(t.numel())
         buf = torch.empty(off, dtype=torch.float32, device=self._dev)
-        self._ema = {"decay": float(decay), "tau": float(tau), "buf": buf, "entries": entries, "poff": poff,
+        self._ema = {"decay": float(decay), "tau": float(tau), "rule": rule, "momentum": float(momentum),
+                     "gamma": float(gamma), "buf": buf, "entries": entries, "poff": poff,
                      "extra": extra, "model": model,
                      "key": lambda: tuple(t.data_ptr() for t, _ in extra)}
+        self._upload_ext()
         self._tables.clear()
         self._seed_ema()
         c = self._counts()
@@ -377,6 +499,7 @@ class _Fused(Optimizer):
         y = {"format": 1, "step": c[0], "ema_step": c[1], "skipped": c[2]}
         if self._ema:
             y["ema_decay"], y["ema_tau"] = self._ema["decay"], self._ema["tau"]
+            y["ema_rule"], y["ema_momentum"], y["ema_gamma"] = (self._ema[k] for k in ("rule", "momentum", "gamma"))
             y["ema"] = {name: self._ema_view(t, off) for name, t, off in self._ema["entries"]}
         sd["yms"] = y
         return sd
@@ -423,14 +546,15 @@ class SGD(_Fused):
     _UNSUPPORTED = ("dampening", "maximize", "foreach", "fused", "differentiable")
 
     def __init__(self, params, lr, momentum=0, nesterov=False, weight_decay=0, *, clip_grad_norm=None,
-                 skip_nonfinite=False, dampening=0, maximize=False, foreach=None, fused=None, differentiable=False):
+                 skip_nonfinite=False, schedule=None, dampening=0, maximize=False, foreach=None, fused=None,
+                 differentiable=False):
         if lr < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError("yms.optim.SGD: lr, momentum and weight_decay must be non-negative")
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                         maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
-        super().__init__(params, defaults, clip_grad_norm, skip_nonfinite)
+        super().__init__(params, defaults, clip_grad_norm, skip_nonfinite, schedule)
 
     def _hyper_row(self, g):
         return (g["lr"], g["momentum"], 0.0, 0.0, g["weight_decay"], 1.0 if g["nesterov"] else 0.0)
@@ -443,22 +567,23 @@ class SGD(_Fused):
 
 
 class Adam(_Fused):
-    """``torch.optim.Adam`` (L2 decay folded into the gradient, not AdamW; no amsgrad) on one launch.
-    ``'step'`` in the state is the optimizer-wide device count (module docstring)."""
+    """``torch.optim.Adam`` (L2 decay folded into the gradient; AdamW is its own class; no amsgrad) on one
+    launch.  ``'step'`` in the state is the optimizer-wide device count (module docstring)."""
     _KIND = L.OPTIM_ADAM
     _STATE_KEYS = ("exp_avg", "exp_avg_sq")
     _UNSUPPORTED = ("amsgrad", "maximize", "foreach", "fused", "capturable", "differentiable",
                     "decoupled_weight_decay")
+    _DECOUPLED = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, *, clip_grad_norm=None,
-                 skip_nonfinite=False, amsgrad=False, maximize=False, foreach=None, fused=None, capturable=False,
-                 differentiable=False):
+                 skip_nonfinite=False, schedule=None, amsgrad=False, maximize=False, foreach=None, fused=None,
+                 capturable=False, differentiable=False):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("yms.optim.Adam: invalid lr / betas / eps / weight_decay")
+            raise ValueError(f"yms.optim.{type(self).__name__}: invalid lr / betas / eps / weight_decay")
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                         maximize=maximize, foreach=foreach, capturable=capturable, differentiable=differentiable,
-                        fused=fused, decoupled_weight_decay=False)
-        super().__init__(params, defaults, clip_grad_norm, skip_nonfinite)
+                        fused=fused, decoupled_weight_decay=self._DECOUPLED)
+        super().__init__(params, defaults, clip_grad_norm, skip_nonfinite, schedule)
 
     def _hyper_row(self, g):
         return (g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], 0.0)
@@ -474,15 +599,41 @@ class Adam(_Fused):
         return int(steps.pop()) if steps else 0
 
 
+class AdamW(Adam):
+    """``torch.optim.AdamW`` (no amsgrad) on one launch: the decay is decoupled, p1 = p (1 - lr wd) with the
+    factor formed in fp64, then Adam's update of p1 from the (clipped) gradient alone, so clipping
+    never scales the decay.  State keys, ``'step'`` and the state dict are Adam's; a
+    ``torch.optim.AdamW`` checkpoint loads here and the reverse."""
+    _KIND = L.OPTIM_ADAMW
+    _UNSUPPORTED = tuple(k for k in Adam._UNSUPPORTED if k != "decoupled_weight_decay")
+    _DECOUPLED = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        super().__init__(params, lr, betas, eps, weight_decay, **kw)
+
+
+def _decay_groups(model, norms=(torch.nn.modules.batchnorm._NormBase,)):
+    """[{decayed parameters}, {norm weights and every bias, weight_decay 0}]"""
+    decay, no_decay = [], []
+    for mod in model.modules():
+        for pname, p in mod.named_parameters(recurse=False):
+            (no_decay if isinstance(mod, norms) or pname == "bias" else decay).append(p)
+    return [{"params": decay}, {"params": no_decay, "weight_decay": 0.0}]
+
+
 def optimizer_config(model, cfg):
     """(class, parameter groups, constructor keywords, EMA keywords or None) for ``cfg['training']``: the
-    keys and defaults of the reference's get_optimizer (tools/utils.py:11-25) plus the optional
-    ``ema: {decay, tau}``, ``clip_grad_norm``, ``skip_nonfinite`` and ``no_decay_bn_bias``."""
+    keys and defaults of the reference's get_optimizer (tools/utils.py:11-25) plus ``optimizer: adamw``
+    and the optional ``ema: {decay, tau}`` or ``ema: {rule: exp_momentum, momentum, gamma}``,
+    ``clip_grad_norm``, ``skip_nonfinite``, ``no_decay_bn_bias`` and ``lr_schedule: {warmup_iters,
+    warmup_start_factor, cosine_begin_iter, cosine_end_iter, min_lr_ratio}`` (a linear warm-up and a cosine
+    to ``min_lr_ratio`` x the learning rate, as two segments under the ``schedule`` keyword)."""
     tr = cfg["training"]
     name = tr["optimizer"].lower()
     lr, wd = tr["learning_rate"], tr["weight_decay"]
-    if name == "adam":
-        cls, kw = Adam, dict(lr=lr, betas=tuple(tr.get("adam_betas", [0.9, 0.999])), weight_decay=wd)
+    if name in ("adam", "adamw"):
+        cls = Adam if name == "adam" else AdamW
+        kw = dict(lr=lr, betas=tuple(tr.get("adam_betas", [0.9, 0.999])), weight_decay=wd)
     elif name == "sgd":
         cls, kw = SGD, dict(lr=lr, momentum=tr.get("sgd_momentum", 0.937), nesterov=tr.get("sgd_nesterov", True),
                             weight_decay=wd)
@@ -490,20 +641,29 @@ def optimizer_config(model, cfg):
         raise ValueError(f"Unsupported optimizer: {name}")
     kw["clip_grad_norm"] = tr.get("clip_grad_norm")
     kw["skip_nonfinite"] = bool(tr.get("skip_nonfinite", False))
+    sch = tr.get("lr_schedule")
+    if sch:
+        segs = []
+        if sch.get("warmup_iters"):
+            segs.append(Segment(0, sch["warmup_iters"], sch.get("warmup_start_factor", 1e-3), 1.0))
+        if sch.get("cosine_end_iter"):
+            segs.append(Segment(sch.get("cosine_begin_iter", 0), sch["cosine_end_iter"], 1.0,
+                                sch.get("min_lr_ratio", 0.0), shape="cosine"))
+        kw["schedule"] = segs
     if tr.get("no_decay_bn_bias"):
         # the YOLOv5 / v8 grouping: BN weights and every bias carry no weight decay
-        decay, no_decay = [], []
-        for mod in model.modules():
-            for pname, p in mod.named_parameters(recurse=False):
-                bn = isinstance(mod, torch.nn.modules.batchnorm._NormBase)
-                (no_decay if bn or pname == "bias" else decay).append(p)
-        groups = [{"params": decay}, {"params": no_decay, "weight_decay": 0.0}]
+        groups = _decay_groups(model)
     else:
         groups = list(model.parameters())
     ema = tr.get("ema")
     if ema is not None and ema is not False:
         ema = dict(ema) if isinstance(ema, dict) else {}
-        ema = {"decay": ema.get("decay", 0.9999), "tau": ema.get("tau", 2000)}
+        if ema.get("rule", "tau") == "exp_momentum":
+            ema = {"rule": "exp_momentum", "momentum": ema.get("momentum", 0.0002), "gamma": ema.get("gamma", 2000)}
+        elif ema.get("rule", "tau") == "tau":
+            ema = {"decay": ema.get("decay", 0.9999), "tau": ema.get("tau", 2000)}
+        else:
+            raise ValueError(f"Unsupported EMA rule: {ema['rule']}")
     else:
         ema = None
     return cls, groups, kw, ema
@@ -515,4 +675,32 @@ def build_optimizer(model, cfg):
     opt = cls(groups, **kw)
     if ema is not None:
         opt.attach_ema(model, **ema)
+    return opt
+
+
+def yolo_ms_recipe_config(model, iters_per_epoch, epochs=300, batch_size=256):
+    """``yolo_ms_recipe``'s (class, parameter groups, constructor keywords, EMA keywords), unbuilt."""
+    norms = (torch.nn.modules.batchnorm._NormBase, torch.nn.GroupNorm, torch.nn.LayerNorm)
+    kw = dict(lr=0.004 * batch_size / 256, betas=(0.9, 0.999), weight_decay=0.05,
+              schedule=[Segment(0, 1000, 1e-5, 1.0),
+                        Segment((epochs // 2) * iters_per_epoch, epochs * iters_per_epoch, 1.0, 0.05, shape="cosine")])
+    return AdamW, _decay_groups(model, norms), kw, {"rule": "exp_momentum", "momentum": 0.0002, "gamma": 2000}
+
+
+def yolo_ms_recipe(model, iters_per_epoch, epochs=300, batch_size=256):
+    """The optimizer of YOLO-MS's training recipe (the RTMDet lineage's), built and with its EMA attached:
+    AdamW at lr 0.004 for batch 256 (scaled linearly with ``batch_size``), weight decay 0.05 and none on
+    norm weights and biases; per iteration, a linear warm-up of the learning rate from 1e-5 x over the first
+    1000 iterations, flat, then a cosine to 0.05 x from epoch ``epochs // 2`` to ``epochs``; the
+    exp-momentum EMA with momentum 0.0002 and gamma 2000.  The schedule runs on the device, so ``step()``
+    uploads nothing and can be captured.
+
+    These values are the published recipe's as this project's maintainers know them.  mmengine, mmdet and
+    mmyolo are not available to this project's tests, so parity with their AdamW / ExpMomentumEMA /
+    LinearLR / CosineAnnealingLR classes is UNPINNED; what the tests pin is the kernels against fp64
+    restatements of the formulas in include/yms.h, torch.optim.AdamW and torch's LinearLR /
+    CosineAnnealingLR.  Not included: the recipe's stage-two augmentation switch, SyncBN."""
+    cls, groups, kw, ema = yolo_ms_recipe_config(model, iters_per_epoch, epochs, batch_size)
+    opt = cls(groups, **kw)
+    opt.attach_ema(model, **ema)
     return opt
