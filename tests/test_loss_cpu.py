@@ -94,3 +94,38 @@ def test_loss_terms_structure():
     bce0 = torch.nn.functional.binary_cross_entropy_with_logits(flat[0, :, 64:], ts)
     assert abs(items["loss_cls"].item() - (2 * bce0.item() + bce1.item()) / 2) < 1e-6
     assert abs(total.item() - (7.5 * items["loss_box"] + 0.5 * items["loss_cls"] + 1.5 * items["loss_dfl"]).item()) < 1e-5
+
+
+def test_det_loss_malformed_calls_never_launch():
+    """Every argument check of yms_det_loss returns before a launch: YMS_ERR_INVALID (1) /
+    YMS_ERR_UNSUPPORTED (2).  The checks are the ones yms_tal_loss and yms_dsl_loss make."""
+    import ctypes
+
+    from yms import _lib as L
+    lib = L.lib()
+    buf = (ctypes.c_float * 16)()
+    P = ctypes.addressof(buf)
+    lv = (ctypes.c_void_p * 5)(*([P] * 5))
+    hs = (ctypes.c_int * 5)(*([2] * 5))
+    st = (ctypes.c_float * 5)(*([8.0] * 5))
+    lam = (ctypes.c_float * 3)(7.5, 0.5, 1.5)
+    need = lib.yms_det_loss_ws_bytes(1, 12, 80, 1)
+    assert need > 0
+    good = dict(dtype=L.BF16, batch=1, nc=80, nlevels=3, maps=lv, grads=None, hs=hs, ws=hs, strides=st, ld=144,
+                targets=P, n_targets=1, img_w=ctypes.c_float(64), img_h=ctypes.c_float(64), iou_type=3,
+                pos_weight=None, lambdas=lam, ws_buf=P, ws_bytes=need, out=P, stream=None)
+
+    def levels(kind, fill, l, v):
+        a = (kind * 5)(*([fill] * 5))
+        a[l] = v
+        return a
+
+    broken = dict(maps=dict(maps=None), hs=dict(hs=None), out=dict(out=None), nlevels0=dict(nlevels=0),
+                  nlevels5=dict(nlevels=5), ld_small=dict(ld=136), ld_mod8=dict(ld=148), iou_type=dict(iou_type=4),
+                  map_null=dict(maps=levels(ctypes.c_void_p, P, 1, None)), hs_zero=dict(hs=levels(ctypes.c_int, 2, 1, 0)),
+                  ws_small=dict(ws_bytes=need - 1))
+    for name, s in dict(zero=0.0, neg=-8.0, inf=math.inf, nan=math.nan).items():
+        broken["stride_" + name] = dict(strides=levels(ctypes.c_float, 8.0, 2, s))
+    for label, change in broken.items():
+        assert lib.yms_det_loss(*[change.get(k, v) for k, v in good.items()]) == 1, label
+    assert lib.yms_det_loss(*[dict(batch=70000).get(k, v) for k, v in good.items()]) == 2

@@ -6,7 +6,8 @@
 //   decode_kernel   per anchor: softmax over each side's 16 DFL bins, expected offsets (grid
 //                   units, loss.py:127-206), decoded (cx, cy, w, h) in pixels
 //   topk_kernel     per target row: plain IoU of every decoded box with the GT (loss.py:252),
-//                   k = min(10, #IoU > 0.1) best anchors (ties -> lower index)  (loss.py:312-315)
+//                   k = min(10, #IoU > 0.1) best anchors (ties -> lower index)  (loss.py:312-315),
+//                   drawn with the block selection primitives of det_loss_common.hpp
 //   assign_kernel   per image, GTs in target order: fg mask, target box / l-t-r-b OVERWRITTEN by
 //                   later GTs, class bits accumulated (loss.py:297-365)
 //   cls_kernel      BCE-with-logits over every anchor x class: per-image sums + gradient
@@ -18,7 +19,8 @@
 //   finalize_kernel per-image means -> batch means -> 7.5 box + 0.5 cls + 1.5 dfl
 //
 // Reductions are deterministic (fixed-order block partials, fp64 finals).  HBM-bound: the head
-// maps are read twice (cls + box) and the gradient written once.
+// maps are read twice (cls + box) and the gradient written once.  The argument checks and the
+// dtype dispatch are the ones of det_loss_common.hpp, shared with tal_loss.hip and dsl_loss.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -69,8 +71,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* tg, int B, int A
   // thread-local top-k, sorted descending (value desc, index asc)
   float bv[DL_TOPK];
   int bi[DL_TOPK];
-#pragma unroll
-  for (int q = 0; q < DL_TOPK; ++q) { bv[q] = -1.f; bi[q] = 0x7fffffff; }
+  sel_clear<true>(bv, bi);
   int cnt = 0;
   const float4* pb = reinterpret_cast<const float4*>(pbox) + (long)b * A;
   for (int a = tid; a < A; a += 256) {
@@ -80,57 +81,17 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* tg, int B, int A
     cxcywh_to_xyxy(c, p);
     const float iou = plain_iou(p, g);
     cnt += iou > DL_IOU_MIN ? 1 : 0;
-    if (iou > bv[DL_TOPK - 1]) {     // strictly greater: an equal later index ranks after
-      float cv = iou;
-      int ci = a;
-#pragma unroll
-      for (int q = 0; q < DL_TOPK; ++q) {
-        if (cv > bv[q]) {
-          const float tv = bv[q];
-          const int ti = bi[q];
-          bv[q] = cv; bi[q] = ci;
-          cv = tv; ci = ti;
-        }
-      }
-    }
+    if (sel_enters<true>(bv, iou)) sel_insert<true>(bv, bi, iou, a);
   }
-  __shared__ int scnt[4];
-  __shared__ float rv[4];
-  __shared__ int ri[4], rt[4];
-  int c = cnt;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-  if ((tid & 63) == 0) scnt[tid >> 6] = c;
-  __syncthreads();
-  const int total = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
+  const int total = block_count_sum(cnt);
   const int k = total < DL_TOPK ? total : DL_TOPK;
   // k rounds of block argmax over each thread's current head (value desc, index asc)
-  int head = 0;
   for (int r = 0; r < k; ++r) {
-    float v = head < DL_TOPK ? bv[0] : -1.f;
-    int ix = head < DL_TOPK ? bi[0] : 0x7fffffff;
-    int owner = tid;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float ov = __shfl_xor(v, m);
-      const int oi = __shfl_xor(ix, m), oo = __shfl_xor(owner, m);
-      if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; owner = oo; }
-    }
-    if ((tid & 63) == 0) { rv[tid >> 6] = v; ri[tid >> 6] = ix; rt[tid >> 6] = owner; }
-    __syncthreads();
-    float wv = rv[0];
-    int wi = ri[0], wo = rt[0];
-    for (int q = 1; q < 4; ++q)
-      if (rv[q] > wv || (rv[q] == wv && ri[q] < wi)) { wv = rv[q]; wi = ri[q]; wo = rt[q]; }
+    float wv;
+    int wi, wo;
+    sel_round<true>(bv[0], bi[0], wv, wi, wo);
     if (tid == 0) kidx[(long)j * DL_TOPK + r] = wi;
-    if (tid == wo) {                  // pop the winner's head
-#pragma unroll
-      for (int q = 0; q < DL_TOPK - 1; ++q) { bv[q] = bv[q + 1]; bi[q] = bi[q + 1]; }
-      bv[DL_TOPK - 1] = -1.f;
-      bi[DL_TOPK - 1] = 0x7fffffff;
-      ++head;
-    }
-    __syncthreads();
+    sel_pop<true>(bv, bi, tid == wo);
   }
   if (tid == 0) kcnt[j] = k;
 }
@@ -407,7 +368,7 @@ struct LossWs {
   size_t pbox, kcnt, kidx, fg, tbox, tltrb, cbits, nfg, pcls, pboxp, flags, img, total;
 };
 static LossWs loss_ws(int B, int A, int nc, int M) {
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+  const auto al = ws_align;
   const int nw = (nc + 31) / 32;
   const int gxc = cdiv((long)A * ((nc + 7) / 8), 256), gxb = cdiv(A, 256);
   LossWs w{};
@@ -463,28 +424,12 @@ yms_status yms_det_loss(int dtype, int batch, int nc, int nlevels, const void* c
                         const int* hs, const int* ws_, const float* strides, int ld, const float* targets,
                         int n_targets, float img_w, float img_h, int iou_type, const float* pos_weight,
                         const float* lambdas, void* ws, size_t ws_bytes, float* out, void* stream) {
-  if (batch <= 0 || nc <= 0 || nlevels <= 0 || nlevels > DL_MAXL || !maps || !hs || !ws_ || !strides || !out ||
-      !lambdas || n_targets < 0 || (n_targets > 0 && !targets) || iou_type < 0 || iou_type > 3)
-    return YMS_ERR_INVALID;
-  if (ld < 4 * DL_DFL + nc || ld % 8) return YMS_ERR_INVALID;
-  long a_total = 0;
-  for (int l = 0; l < nlevels; ++l) a_total += (long)hs[l] * ws_[l];
-  if (a_total * ((nc + 7) / 8) >= (1l << 31) - 256) return YMS_ERR_UNSUPPORTED;
-  LossLevels L{};
-  L.nl = nlevels;
-  L.ld = ld;
-  int A = 0;
-  for (int l = 0; l < nlevels; ++l) {
-    if (!maps[l] || hs[l] <= 0 || ws_[l] <= 0) return YMS_ERR_INVALID;
-    L.x[l] = maps[l];
-    L.g[l] = grads ? grads[l] : nullptr;
-    L.h[l] = hs[l];
-    L.w[l] = ws_[l];
-    L.stride[l] = strides[l];
-    L.off[l] = A;
-    A += hs[l] * ws_[l];
-  }
-  L.off[nlevels] = A;
+  if (!out || !lambdas || !map_dtype_ok(dtype) || iou_type < 0 || iou_type > 3) return YMS_ERR_INVALID;
+  LossLevels L;
+  int A;
+  const yms_status bad = loss_levels(batch, nc, nlevels, maps, grads, hs, ws_, strides, ld, targets, n_targets,
+                                     img_w, img_h, L, A);
+  if (bad != YMS_OK) return bad;
   const LossWs w = loss_ws(batch, A, nc, n_targets);
   if (!ws || ws_bytes < w.total) return YMS_ERR_INVALID;
   char* base = (char*)ws;
@@ -504,31 +449,24 @@ yms_status yms_det_loss(int dtype, int batch, int nc, int nlevels, const void* c
   const int gxc = cdiv((long)A * ((nc + 7) / 8), 256), gxb = cdiv(A, 256);
   hipStream_t st = (hipStream_t)stream;
   const float gscale = lambdas[1] / ((float)batch * (float)A * (float)nc);
-#define YMS_LOSS_CASE(T)                                                                                        \
-  hipLaunchKernelGGL(decode_kernel<T>, dim3(gxb, batch), dim3(256), 0, st, L, A, pbox);                        \
-  if (n_targets > 0)                                                                                           \
-    hipLaunchKernelGGL(topk_kernel, dim3(n_targets), dim3(256), 0, st, targets, batch, A, img_w, img_h, pbox,  \
-                       kcnt, kidx);                                                                            \
-  hipLaunchKernelGGL(assign_kernel, dim3(batch), dim3(256), 0, st, targets, n_targets, A, nc, nw, img_w, img_h, \
-                     L, kcnt, kidx, fg, tbox, tltrb, cbits, nfg);                                              \
-  hipLaunchKernelGGL(cls_kernel<T>, dim3(gxc, batch), dim3(256), 0, st, L, A, nc, nw, cbits, nfg, pos_weight,  \
-                     gscale, pcls);                                                                            \
-  hipLaunchKernelGGL(box_kernel<T>, dim3(gxb, batch), dim3(256), 0, st, L, A, fg, tbox, tltrb, iou_type,        \
-                     pboxp);                                                                                   \
-  hipLaunchKernelGGL(flags_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, st, batch, gxb, pboxp, flags);           \
-  if (grads)                                                                                                   \
-    hipLaunchKernelGGL(boxgrad_kernel<T>, dim3(gxb, batch), dim3(256), 0, st, L, A, fg, tbox, tltrb, iou_type,  \
-                       flags, lambdas[0], lambdas[2], batch, nfg);                                             \
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, batch, A, nc, gxc, pcls, gxb, pboxp, nfg,      \
-                     lambdas[0], lambdas[1], lambdas[2], img, out);
-  switch (dtype) {
-    case YMS_F32: { YMS_LOSS_CASE(float) break; }
-    case YMS_BF16: { YMS_LOSS_CASE(bf16) break; }
-    case YMS_F16: { YMS_LOSS_CASE(f16) break; }
-    default: return YMS_ERR_INVALID;
-  }
-#undef YMS_LOSS_CASE
-  return launch_status();
+  return launch_for_dtype(dtype, [&](auto map_type) {
+    using T = typename decltype(map_type)::type;
+    hipLaunchKernelGGL(decode_kernel<T>, dim3(gxb, batch), dim3(256), 0, st, L, A, pbox);
+    if (n_targets > 0)
+      hipLaunchKernelGGL(topk_kernel, dim3(n_targets), dim3(256), 0, st, targets, batch, A, img_w, img_h, pbox, kcnt,
+                         kidx);
+    hipLaunchKernelGGL(assign_kernel, dim3(batch), dim3(256), 0, st, targets, n_targets, A, nc, nw, img_w, img_h, L,
+                       kcnt, kidx, fg, tbox, tltrb, cbits, nfg);
+    hipLaunchKernelGGL(cls_kernel<T>, dim3(gxc, batch), dim3(256), 0, st, L, A, nc, nw, cbits, nfg, pos_weight,
+                       gscale, pcls);
+    hipLaunchKernelGGL(box_kernel<T>, dim3(gxb, batch), dim3(256), 0, st, L, A, fg, tbox, tltrb, iou_type, pboxp);
+    hipLaunchKernelGGL(flags_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, st, batch, gxb, pboxp, flags);
+    if (grads)
+      hipLaunchKernelGGL(boxgrad_kernel<T>, dim3(gxb, batch), dim3(256), 0, st, L, A, fg, tbox, tltrb, iou_type,
+                         flags, lambdas[0], lambdas[2], batch, nfg);
+    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, batch, A, nc, gxc, pcls, gxb, pboxp, nfg,
+                       lambdas[0], lambdas[1], lambdas[2], img, out);
+  });
 }
 
 yms_status yms_scale_by_device_scalar(int dtype, int nbuf, void* const* bufs, const long* counts, const float* g,
@@ -543,13 +481,10 @@ yms_status yms_scale_by_device_scalar(int dtype, int nbuf, void* const* bufs, co
     mx = std::max(mx, counts[i]);
   }
   const dim3 grid((unsigned)std::max<long>(1, std::min<long>(1024, cdiv(mx, 256))), (unsigned)nbuf);
-  switch (dtype) {
-    case YMS_F32: hipLaunchKernelGGL(scale_by_dev_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, b, g); break;
-    case YMS_BF16: hipLaunchKernelGGL(scale_by_dev_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, b, g); break;
-    case YMS_F16: hipLaunchKernelGGL(scale_by_dev_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, b, g); break;
-    default: return YMS_ERR_INVALID;
-  }
-  return launch_status();
+  return launch_for_dtype(dtype, [&](auto map_type) {
+    hipLaunchKernelGGL(scale_by_dev_kernel<typename decltype(map_type)::type>, grid, dim3(256), 0,
+                       (hipStream_t)stream, b, g);
+  });
 }
 
 }  // extern "C"

@@ -1,8 +1,12 @@
-// Device helpers shared by the detection losses (det_loss.hip: the reference's ComputeLoss;
-// tal_loss.hip: the task-aligned assigner loss; dsl_loss.hip: the dynamic soft-label assigner loss): head-map addressing, the DFL softmax, the IoU
-// family with its analytic gradient, BCE-with-logits and the fixed-order block sum.
+// Shared by the three detection losses (det_loss.hip: the reference's ComputeLoss; tal_loss.hip:
+// the task-aligned assigner loss; dsl_loss.hip: the dynamic soft-label assigner loss).  Device:
+// head-map addressing, the DFL softmax, the IoU family with its analytic gradient, BCE-with-logits,
+// the fixed-order block sum and the block selection primitives (sorted insert, arg-extreme round,
+// pop, count sum).  Host: the entries' argument checks and LossLevels fill, the dispatch on the map
+// dtype.  What only the two assigner losses share is in assign_loss_common.hpp.
 #pragma once
 #include <cmath>
+#include <cstddef>
 
 #include "yms_common.hpp"
 
@@ -223,110 +227,188 @@ __device__ __forceinline__ void block_sum_store(float v, float* part, long slot)
   __syncthreads();
 }
 
-// ---- shared by the anchor-based assigner losses (tal_loss.hip, dsl_loss.hip) ------------------
-constexpr float TAL_INSIDE_EPS = 1e-9f;
-constexpr float TAL_DFL_MAX = (float)(DL_DFL - 1) - 0.01f;
+// ---- block selection: every thread of a 256-thread block keeps a short sorted list of (value,
+// index) and the block draws the lists' best entries one round at a time.  DESC: largest value
+// first (sentinel -1, every real value is >= 0), else smallest first (sentinel +inf); equal values
+// rank by lower index.  The exchange slots are shared by every call within one kernel.
+constexpr int SEL_NONE = 0x7fffffff;     // index of a sentinel entry
+template <bool DESC>
+__device__ __forceinline__ float sel_sentinel() { return DESC ? -1.f : INFINITY; }
+template <bool DESC>
+__device__ __forceinline__ bool sel_before(float a, float b) { return DESC ? a > b : a < b; }
 
-// target row -> false when ignored (image outside [0, B) or class outside [0, nc)); image, class
-// and the GT's xyxy box in pixels
-__device__ __forceinline__ bool tal_row(const float* t, int B, int nc, float img_w, float img_h, int& b, int& cls,
-                                        float (&g)[4]) {
-  if (!(t[0] >= 0.f && t[0] < (float)B && t[1] >= 0.f && t[1] < (float)nc)) return false;
-  b = (int)t[0];
-  cls = (int)t[1];
-  const float gc[4] = {t[2] * img_w, t[3] * img_h, t[4] * img_w, t[5] * img_h};
-  cxcywh_to_xyxy(gc, g);
-  return true;
-}
-
-__device__ __forceinline__ bool tal_inside(float ax, float ay, const float (&g)[4]) {
-  return fminf(fminf(ax - g[0], ay - g[1]), fminf(g[2] - ax, g[3] - ay)) > TAL_INSIDE_EPS;
-}
-
-// block b of 256 threads: image b's valid target rows in target order -> rows[b * M ..], nrows[b]
-// (global memory, so no limit on the rows of one image)
-__device__ __forceinline__ void tal_list_rows(const float* tg, int M, int B, int nc, int* rows, int* nrows) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  int* mine = rows + (long)b * M;
-  __shared__ int wcnt[4];
-  int base = 0;
-  for (int j0 = 0; j0 < M; j0 += 256) {
-    const int j = j0 + tid;
-    bool hit = false;
-    if (j < M) {
-      const float* t = tg + (long)j * 6;
-      hit = t[0] >= 0.f && t[0] < (float)B && t[1] >= 0.f && t[1] < (float)nc && (int)t[0] == b;
-    }
-    const unsigned long long bal = __ballot(hit);
-    if ((tid & 63) == 0) wcnt[tid >> 6] = __popcll(bal);
-    __syncthreads();
-    int pos = base;
-    for (int q = 0; q < (tid >> 6); ++q) pos += wcnt[q];
-    if (hit) mine[pos + __popcll(bal & ((1ull << (tid & 63)) - 1ull))] = j;
-    base += (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-    __syncthreads();
-  }
-  if (tid == 0) nrows[b] = base;
-}
-
-// fixed-order fp64 sum of one value per thread over a 256-thread block -> every thread
-__device__ __forceinline__ double tal_block_sum(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
-// 1 - IoU-family value (IOU: box_iou_grad's iou_type) and the DFL value (1/4 of the sides' two-bin cross entropies) of one foreground anchor
-// and, GRAD, d/d logits scaled by sb, sd, left in v
-template <bool GRAD, int IOU>
-__device__ __forceinline__ void tal_box_dfl(float (&v)[4 * DL_DFL], float ax, float ay, float stride,
-                                            const float (&g)[4], float sb, float sd, float& lbox, float& ldfl) {
-  // DFL targets in stride units, clamped into the bins, read before the softmax
-  const float dist[4] = {ax - g[0], ay - g[1], g[2] - ax, g[3] - ay};
-  int li[4];
-  float wl[4], wr[4], xl[4], xr[4];
+template <bool DESC, int N>
+__device__ __forceinline__ void sel_clear(float (&v)[N]) {
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float d = fminf(fmaxf(dist[s] / stride, 0.f), TAL_DFL_MAX);
-    const float fl = floorf(d);
-    wr[s] = d - fl;
-    wl[s] = 1.0f - wr[s];
-    li[s] = (int)fl;                    // 0..14: the right bin li + 1 <= 15
-    xl[s] = xr[s] = 0.f;
+  for (int q = 0; q < N; ++q) v[q] = sel_sentinel<DESC>();
+}
+template <bool DESC, int N>
+__device__ __forceinline__ void sel_clear(float (&v)[N], int (&ix)[N]) {
 #pragma unroll
-    for (int i = 0; i < DL_DFL; ++i) {  // selects, not a runtime index: v stays in registers
-      xl[s] = i == li[s] ? v[s * DL_DFL + i] : xl[s];
-      xr[s] = i == li[s] + 1 ? v[s * DL_DFL + i] : xr[s];
+  for (int q = 0; q < N; ++q) { v[q] = sel_sentinel<DESC>(); ix[q] = SEL_NONE; }
+}
+
+// thread-local sorted insert, in two steps: `if (sel_enters<DESC>(v, x)) sel_insert<DESC>(v, ix, x, i);`
+// (the test stays at the call site: folded into sel_insert, the compiler reuses its load of the tail
+// for the last step of the insert and the three selection kernels need 4 to 17 more registers).
+// A thread meets its indices in ascending order, so the strict comparisons keep the earlier of
+// equals first (an equal later index ranks after); NaN never enters.
+template <bool DESC, int N>
+__device__ __forceinline__ bool sel_enters(const float (&v)[N], float x) { return sel_before<DESC>(x, v[N - 1]); }
+template <bool DESC, int N>
+__device__ __forceinline__ void sel_insert(float (&v)[N], int (&ix)[N], float cv, int ci) {
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    if (sel_before<DESC>(cv, v[q])) {
+      const float tv = v[q];
+      const int ti = ix[q];
+      v[q] = cv; ix[q] = ci;
+      cv = tv; ci = ti;
     }
   }
-  float e[4], lse[4];
-  dfl_softmax(v, e, lse);     // v: probabilities
-  const float p[4] = {ax - e[0] * stride, ay - e[1] * stride, ax + e[2] * stride, ay + e[3] * stride};
-  float dp[4];
-  lbox = 1.f - box_iou_grad<GRAD>(p, g, IOU, dp);
-  float dfl = 0.f;
+}
+// the same for values alone
+template <bool DESC, int N>
+__device__ __forceinline__ void sel_insert(float (&v)[N], float cv) {
 #pragma unroll
-  for (int s = 0; s < 4; ++s) dfl += (lse[s] - xl[s]) * wl[s] + (lse[s] - xr[s]) * wr[s];
-  ldfl = 0.25f * dfl;
-  if (GRAD) {
-    // loss 1 - val -> d/dp = -dp; p0 = ax - e0 s (d/de0 = -s), p2 = ax + e2 s (d/de2 = s)
-    const float k = sb * stride;
-    const float ge[4] = {dp[0] * k, dp[1] * k, -dp[2] * k, -dp[3] * k};
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < DL_DFL; ++i) {
-        const float pr = v[s * DL_DFL + i];
-        float gi = ge[s] * pr * ((float)i - e[s]);      // d e_s / d logit_i = p_i (i - e_s)
-        gi += sd * (pr - (i == li[s] ? wl[s] : 0.f) - (i == li[s] + 1 ? wr[s] : 0.f));
-        v[s * DL_DFL + i] = gi;
-      }
+  for (int q = 0; q < N; ++q) {
+    if (sel_before<DESC>(cv, v[q])) { const float tv = v[q]; v[q] = cv; cv = tv; }
   }
 }
+
+// one round: block arg-extreme over every thread's list head (v, ix) -> the winner's value, index
+// and owner thread, to every thread: value first, then lower index.  INDEXED = false is the round
+// of a list of values alone (below): value first, then lower owner thread, and no index travels;
+// the waves' winners are scanned in ascending owner order, so there the strict comparison suffices.
+// The caller pops the owner's head with sel_pop, whose barrier frees the slots for the next round.
+struct SelSlots {
+  float rv[4];
+  int ri[4], rt[4];
+};
+__device__ __forceinline__ SelSlots& sel_slots() {     // one set per kernel, whatever rounds it runs
+  __shared__ SelSlots s;
+  return s;
+}
+template <bool DESC, bool INDEXED = true>
+__device__ __forceinline__ void sel_round(float v, int ix, float& wv, int& wi, int& wo) {
+  SelSlots& s = sel_slots();
+  const int tid = threadIdx.x;
+  int owner = tid;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float ov = __shfl_xor(v, m);
+    const int oo = __shfl_xor(owner, m), oi = INDEXED ? __shfl_xor(ix, m) : oo;
+    if (sel_before<DESC>(ov, v) || (ov == v && oi < (INDEXED ? ix : owner))) { v = ov; ix = oi; owner = oo; }
+  }
+  if ((tid & 63) == 0) {
+    s.rv[tid >> 6] = v;
+    s.rt[tid >> 6] = owner;
+    if (INDEXED) s.ri[tid >> 6] = ix;
+  }
+  __syncthreads();
+  wv = s.rv[0];
+  wo = s.rt[0];
+  wi = INDEXED ? s.ri[0] : wo;
+  for (int q = 1; q < 4; ++q)
+    if (sel_before<DESC>(s.rv[q], wv) || (INDEXED && s.rv[q] == wv && s.ri[q] < wi)) {
+      wv = s.rv[q];
+      wo = s.rt[q];
+      wi = INDEXED ? s.ri[q] : wo;
+    }
+}
+template <bool DESC>
+__device__ __forceinline__ void sel_round(float v, float& wv, int& wo) {
+  int wi;
+  sel_round<DESC, false>(v, 0, wv, wi, wo);
+}
+
+// pop the head of the thread for which `mine` holds (the round's owner); the list refills with
+// sentinels, so an emptied list offers the sentinel.  Every thread of the block calls it.
+template <bool DESC, int N>
+__device__ __forceinline__ void sel_pop(float (&v)[N], int (&ix)[N], bool mine) {
+  if (mine) {
+#pragma unroll
+    for (int q = 0; q < N - 1; ++q) { v[q] = v[q + 1]; ix[q] = ix[q + 1]; }
+    v[N - 1] = sel_sentinel<DESC>();
+    ix[N - 1] = SEL_NONE;
+  }
+  __syncthreads();
+}
+template <bool DESC, int N>
+__device__ __forceinline__ void sel_pop(float (&v)[N], bool mine) {
+  if (mine) {
+#pragma unroll
+    for (int q = 0; q < N - 1; ++q) v[q] = v[q + 1];
+    v[N - 1] = sel_sentinel<DESC>();
+  }
+  __syncthreads();
+}
+
+// sum of one int per thread over the block's four waves -> every thread
+__device__ __forceinline__ int block_count_sum(int c) {
+  __shared__ int scnt[4];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+  if ((threadIdx.x & 63) == 0) scnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  return (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
+}
+
+// ---- host side, shared by the three entries --------------------------------------------------
+// Argument checks common to yms_det_loss / yms_tal_loss / yms_dsl_loss (YMS_ERR_INVALID before
+// YMS_ERR_UNSUPPORTED), then the levels and the anchor count.  Returns before any launch.
+inline yms_status loss_levels(int batch, int nc, int nlevels, const void* const* maps, void* const* grads,
+                              const int* hs, const int* ws_, const float* strides, int ld, const float* targets,
+                              int n_targets, float img_w, float img_h, LossLevels& L, int& A) {
+  if (batch <= 0 || nc <= 0 || nlevels <= 0 || nlevels > DL_MAXL || !maps || !hs || !ws_ || !strides ||
+      n_targets < 0 || (n_targets > 0 && !targets))
+    return YMS_ERR_INVALID;
+  if (!(img_w > 0.f) || !(img_h > 0.f) || !std::isfinite(img_w) || !std::isfinite(img_h)) return YMS_ERR_INVALID;
+  if (ld < 4 * DL_DFL + nc || ld % 8) return YMS_ERR_INVALID;
+  long a_total = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    if (!maps[l] || hs[l] <= 0 || ws_[l] <= 0 || !(strides[l] > 0.f) || !std::isfinite(strides[l]))
+      return YMS_ERR_INVALID;
+    if (grads && !grads[l]) return YMS_ERR_INVALID;
+    a_total += (long)hs[l] * ws_[l];
+    if (a_total >= (1l << 31)) return YMS_ERR_UNSUPPORTED;
+  }
+  if (a_total * ((nc + 7) / 8) >= (1l << 31) - 256) return YMS_ERR_UNSUPPORTED;
+  if (batch > 65535) return YMS_ERR_UNSUPPORTED;          // images are the grid's y dimension
+  L = LossLevels{};
+  L.nl = nlevels;
+  L.ld = ld;
+  A = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    L.x[l] = maps[l];
+    L.g[l] = grads ? grads[l] : nullptr;
+    L.h[l] = hs[l];
+    L.w[l] = ws_[l];
+    L.stride[l] = strides[l];
+    L.off[l] = A;
+    A += hs[l] * ws_[l];
+  }
+  L.off[nlevels] = A;
+  return YMS_OK;
+}
+
+inline bool map_dtype_ok(int dtype) { return dtype == YMS_F32 || dtype == YMS_BF16 || dtype == YMS_F16; }
+
+// launches(MapType<T>{}) with T the element type of `dtype` (map_dtype_ok), then the launch status
+template <typename T>
+struct MapType { using type = T; };
+template <typename F>
+inline yms_status launch_for_dtype(int dtype, F&& launches) {
+  switch (dtype) {
+    case YMS_F32: launches(MapType<float>{}); break;
+    case YMS_BF16: launches(MapType<bf16>{}); break;
+    case YMS_F16: launches(MapType<f16>{}); break;
+    default: return YMS_ERR_INVALID;
+  }
+  return launch_status();
+}
+
+// 256-aligned pieces of a workspace
+inline size_t ws_align(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace yms

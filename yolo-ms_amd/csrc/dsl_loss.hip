@@ -3,7 +3,7 @@
 // tests/dsl_ref.py, which is the definition; DESIGN.md "Dynamic soft-label loss"), fused with its
 // analytic gradient like tal_loss.hip.
 //
-//   dsl_rows_kernel      per image: its valid target rows, in target order, listed in global memory
+//   assign_rows_kernel   per image: its valid target rows, in target order, listed in global memory
 //   dsl_decode_kernel    per anchor: DFL softmax -> predicted xyxy box in pixels; S(a) = sum over the
 //                        classes of the background QFL softplus(x) sigmoid(x)^beta (the class logits
 //                        are read once here, not once per GT); candidate flag = the centre lies inside
@@ -17,13 +17,15 @@
 //   dsl_resolve_kernel   per anchor: one claim -> that GT; several -> the GT of lowest cost among ALL
 //                        the image's valid GTs (lowest row on a tie), also one that did not claim it;
 //                        t = IoU of the final pair, its class; block partial sums of t
-//   dsl_norm_kernel      one block: norm = max(sum t, 1) in fp64, fixed order
-//   dsl_cls_kernel       QFL of every anchor x class (target t at the assigned class, 0 elsewhere),
-//                        gradient scaled by cls_gain / norm (read from device memory)
-//   dsl_box_kernel       per foreground anchor: (1 - GIoU) t and the two-bin DFL cross entropy t, and
-//                        their gradient into the 64 DFL logits (zeros for background anchors)
-//   dsl_finalize_kernel  fp64 fixed-order sums / norm -> total, box, cls, dfl, norm
+// and then the tail it shares with tal_loss.hip (assign_loss_common.hpp, where the rows kernel is too):
+//   assign_norm_kernel   one block: norm = max(sum t, 1) in fp64, fixed order
+//   assign_cls_kernel    <DslQfl> QFL of every anchor x class (target t at the assigned class, 0
+//                        elsewhere), gradient scaled by cls_gain / norm (read from device memory)
+//   assign_box_kernel    <GIoU> per foreground anchor: (1 - GIoU) t and the two-bin DFL cross entropy t,
+//                        and their gradient into the 64 DFL logits (zeros for background anchors)
+//   assign_finalize_kernel  fp64 fixed-order sums / norm -> total, box, cls, dfl, norm
 //
+// The lists and rounds of dsl_select_kernel are the block selection primitives of det_loss_common.hpp.
 // The cost of a pair comes from ONE function, dsl_pair, for selection and resolution alike, so the
 // two passes rank identically.  Deterministic: integer atomics only, fixed-order partials, fp64
 // finals.  No host sync.  Target rows are never staged in LDS, so there is no row limit.
@@ -31,7 +33,7 @@
 #include <climits>
 #include <cmath>
 
-#include "det_loss_common.hpp"
+#include "assign_loss_common.hpp"
 
 namespace yms {
 
@@ -165,8 +167,8 @@ __global__ __launch_bounds__(256) void dsl_select_kernel(LossLevels L, const flo
   // its anchors in ascending index, so a strict comparison keeps the earlier of equals first
   float tv[DSL_TOPK], cv[DSL_TOPK];
   int ci[DSL_TOPK];
-#pragma unroll
-  for (int q = 0; q < DSL_TOPK; ++q) { tv[q] = -1.f; cv[q] = INFINITY; ci[q] = 0x7fffffff; }
+  sel_clear<true>(tv);
+  sel_clear<false>(cv, ci);
   int ncand = 0;
   const float4* pb = reinterpret_cast<const float4*>(pbox) + (long)b * A;
   const float* Sb = S + (long)b * A;
@@ -218,43 +220,17 @@ __global__ __launch_bounds__(256) void dsl_select_kernel(LossLevels L, const flo
       const long row = anchor_row(L, b, a, l, ax, ay);
       const float4 p4 = pb[a];
       const float iou = dsl_iou(p4, g);
-      if (iou > tv[DSL_TOPK - 1]) {
-        float v = iou;
-#pragma unroll
-        for (int q = 0; q < DSL_TOPK; ++q) {
-          if (v > tv[q]) { const float t_ = tv[q]; tv[q] = v; v = t_; }
-        }
-      }
+      if (sel_enters<true>(tv, iou)) sel_insert<true>(tv, iou);
       // margin: S - background term and the box term may round below 0 by ~1e-6 of their size
       if (!(dsl_prior(ax, ay, L.stride[l], g, P.radius) > bound * 1.0001f + 1.f)) {
         const float xc = to_f(reinterpret_cast<const T*>(L.x[l])[row + 4 * DL_DFL + cls]);
         float iou_;
         const float cost = dsl_pair(p4, Sb[a], xc, ax, ay, L.stride[l], g, P, iou_);
-        if (cost < cv[DSL_TOPK - 1]) {     // strictly less: an equal later index ranks after; NaN never enters
-          float v = cost;
-          int ix = a;
-#pragma unroll
-          for (int q = 0; q < DSL_TOPK; ++q) {
-            if (v < cv[q]) {
-              const float t_ = cv[q];
-              const int i_ = ci[q];
-              cv[q] = v; ci[q] = ix;
-              v = t_; ix = i_;
-            }
-          }
-        }
+        if (sel_enters<false>(cv, cost)) sel_insert<false>(cv, ci, cost, a);
       }
     }
   }
-  __shared__ int scnt[4];
-  __shared__ float rv[4];
-  __shared__ int ri[4], rt[4];
-  int c = ncand;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-  if ((tid & 63) == 0) scnt[tid >> 6] = c;
-  __syncthreads();
-  const int total = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
+  const int total = block_count_sum(ncand);
   if (total == 0) {                                   // no candidate in the image: nothing assigned
     if (tid == 0 && dyn_k) dyn_k[j] = 0;
     return;
@@ -263,60 +239,26 @@ __global__ __launch_bounds__(256) void dsl_select_kernel(LossLevels L, const flo
   // summed in fp64 in descending order by every thread alike
   const int n = total < P.topk ? total : P.topk;
   double ssum = 0.0;
-  for (int r = 0; r < n; ++r) {
-    float v = tv[0];
-    int owner = tid;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float ov = __shfl_xor(v, m);
-      const int oo = __shfl_xor(owner, m);
-      if (ov > v || (ov == v && oo < owner)) { v = ov; owner = oo; }
-    }
-    if ((tid & 63) == 0) { rv[tid >> 6] = v; rt[tid >> 6] = owner; }
-    __syncthreads();
-    float wv = rv[0];
-    int wo = rt[0];
-    for (int q = 1; q < 4; ++q)
-      if (rv[q] > wv) { wv = rv[q]; wo = rt[q]; }
+  for (int r = 0; r < n; ++r) {     // value desc, then lower owner thread
+    float wv;
+    int wo;
+    sel_round<true>(tv[0], wv, wo);
     ssum += (double)fmaxf(wv, 0.f);
-    if (tid == wo) {
-#pragma unroll
-      for (int q = 0; q < DSL_TOPK - 1; ++q) tv[q] = tv[q + 1];
-      tv[DSL_TOPK - 1] = -1.f;
-    }
-    __syncthreads();
+    sel_pop<true>(tv, tid == wo);
   }
   int k = (int)floor(ssum);
   k = k < 1 ? 1 : (k > n ? n : k);
   if (tid == 0 && dyn_k) dyn_k[j] = k;
   // k rounds of block argmin over each thread's current head (cost asc, anchor asc)
   for (int r = 0; r < k; ++r) {
-    float v = cv[0];
-    int ix = ci[0];
-    int owner = tid;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float ov = __shfl_xor(v, m);
-      const int oi = __shfl_xor(ix, m), oo = __shfl_xor(owner, m);
-      if (ov < v || (ov == v && oi < ix)) { v = ov; ix = oi; owner = oo; }
-    }
-    if ((tid & 63) == 0) { rv[tid >> 6] = v; ri[tid >> 6] = ix; rt[tid >> 6] = owner; }
-    __syncthreads();
-    float wv = rv[0];
-    int wi = ri[0], wo = rt[0];
-    for (int q = 1; q < 4; ++q)
-      if (rv[q] < wv || (rv[q] == wv && ri[q] < wi)) { wv = rv[q]; wi = ri[q]; wo = rt[q]; }
+    float wv;
+    int wi, wo;
+    sel_round<false>(cv[0], ci[0], wv, wi, wo);
     if (tid == 0 && (unsigned)wi < (unsigned)A) {
       atomicAdd(&cnt[(long)b * A + wi], 1);
       atomicMin(&agt[(long)b * A + wi], j);
     }
-    if (tid == wo && (unsigned)wi < (unsigned)A) {      // pop the winner's head
-#pragma unroll
-      for (int q = 0; q < DSL_TOPK - 1; ++q) { cv[q] = cv[q + 1]; ci[q] = ci[q + 1]; }
-      cv[DSL_TOPK - 1] = INFINITY;
-      ci[DSL_TOPK - 1] = 0x7fffffff;
-    }
-    __syncthreads();
+    sel_pop<false>(cv, ci, tid == wo && (unsigned)wi < (unsigned)A);
   }
 }
 
@@ -372,136 +314,21 @@ __global__ __launch_bounds__(256) void dsl_resolve_kernel(LossLevels L, const fl
   block_sum_store(t, part, (long)b * gridDim.x + blockIdx.x);
 }
 
-__global__ __launch_bounds__(256) void dsl_norm_kernel(long n, const float* part, float* norm) {
-  __shared__ double sh[256];
-  double s = 0.0;
-  for (long i = threadIdx.x; i < n; i += 256) s += (double)part[i];
-  const double tot = tal_block_sum(s, sh);
-  if (threadIdx.x == 0) norm[0] = (float)fmax(tot, 1.0);
-}
+// per-logit term of assign_cls_kernel: the quality focal term
+struct DslQfl {
+  float beta;
+  __device__ __forceinline__ float operator()(float x, float t, float& dx) const { return dsl_qfl(x, t, beta, dx); }
+};
 
-// QFL over anchors x classes against the soft labels: thread = (anchor, 8-class chunk)
-template <typename T>
-__global__ __launch_bounds__(256) void dsl_cls_kernel(LossLevels L, int A, int nc, float beta, const float* tsc,
-                                                      const int* acls, const float* norm, float gnum, float* part) {
-  const int b = blockIdx.y;
-  const int G = (nc + 7) / 8;
-  const int i = blockIdx.x * 256 + threadIdx.x;       // A * G < 2^31 (host-checked): 32-bit division
-  float acc = 0.f;
-  if (i < A * G) {
-    const int a = i / G, q = i - a * G;
-    const int c0 = q * 8, nv = min(8, nc - c0);
-    int l;
-    float ax, ay;
-    const long row = anchor_row(L, b, a, l, ax, ay) + 4 * DL_DFL + c0;
-    float x[8];
-    load8(reinterpret_cast<const T*>(L.x[l]) + row, nv, x);
-    const int ac = acls[(long)b * A + a];
-    const float t = tsc[(long)b * A + a];
-    const float gscale = gnum / norm[0];
-    float gr[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      gr[k] = 0.f;
-      if (k < nv) {
-        float dx;
-        acc += dsl_qfl(x[k], c0 + k == ac ? t : 0.f, beta, dx);
-        gr[k] = dx * gscale;
-      }
-    }
-    if (L.g[l]) store8(reinterpret_cast<T*>(L.g[l]) + row, nv, gr);
-  }
-  block_sum_store(acc, part, (long)b * gridDim.x + blockIdx.x);
-}
-
-// per anchor: weighted box and DFL sums and, GRAD, their gradient into the 64 DFL logits
-template <typename T, bool GRAD>
-__global__ __launch_bounds__(256) void dsl_box_kernel(LossLevels L, const float* tg, int M, int B, int A, int nc,
-                                                      float img_w, float img_h, const int* agt, const float* tsc,
-                                                      const float* norm, float nbox, float ndfl, float* part) {
-  const int a = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-  float lb = 0.f, ld = 0.f;
-  if (a < A) {
-    const long i = (long)b * A + a;
-    const int j = agt[i];
-    int l;
-    float ax, ay;
-    const long row = anchor_row(L, b, a, l, ax, ay);
-    float v[4 * DL_DFL];
-    int tb, cls;
-    float g[4];
-    bool fg = false;
-    if (j >= 0 && j < M && tal_row(tg + (long)j * 6, B, nc, img_w, img_h, tb, cls, g)) {
-      fg = true;
-      load_dist(reinterpret_cast<const T*>(L.x[l]) + row, v);
-      const float t = tsc[i];
-      const float it = GRAD ? t / norm[0] : 0.f;
-      float vb, vd;
-      tal_box_dfl<GRAD, 1>(v, ax, ay, L.stride[l], g, nbox * it, ndfl * it, vb, vd);
-      lb = vb * t;
-      ld = vd * t;
-    }
-    if (GRAD && L.g[l]) {
-      if (!fg) {
-#pragma unroll
-        for (int q = 0; q < 4 * DL_DFL; ++q) v[q] = 0.f;
-      }
-      store_dist(reinterpret_cast<T*>(L.g[l]) + row, v);
-    }
-  }
-  const long slot = ((long)b * gridDim.x + blockIdx.x) * 2;
-  block_sum_store(lb, part, slot + 0);
-  block_sum_store(ld, part, slot + 1);
-}
-
-__global__ __launch_bounds__(256) void dsl_finalize_kernel(long ncls, const float* pcls, long nbox, const float* pbox,
-                                                           const float* norm, float g_box, float g_cls, float g_dfl,
-                                                           float* out) {
-  __shared__ double sh[256];
-  double sc = 0.0, sb = 0.0, sd = 0.0;
-  for (long i = threadIdx.x; i < ncls; i += 256) sc += (double)pcls[i];
-  for (long i = threadIdx.x; i < nbox; i += 256) { sb += (double)pbox[2 * i]; sd += (double)pbox[2 * i + 1]; }
-  sc = tal_block_sum(sc, sh);
-  sb = tal_block_sum(sb, sh);
-  sd = tal_block_sum(sd, sh);
-  if (threadIdx.x != 0) return;
-  const double n = (double)norm[0];
-  const double lcls = sc / n, lbox = sb / n, ldfl = sd / n;
-  out[0] = (float)(g_box * lbox + g_cls * lcls + g_dfl * ldfl);
-  out[1] = (float)lbox;
-  out[2] = (float)lcls;
-  out[3] = (float)ldfl;
-  out[4] = (float)n;
-}
-
-__global__ __launch_bounds__(256) void dsl_rows_kernel(const float* tg, int M, int B, int nc, int* rows, int* nrows) {
-  tal_list_rows(tg, M, B, nc, rows, nrows);
-}
-
-// workspace layout (bytes, 256-aligned pieces)
+// workspace: the common pieces, then the background sums and the candidate flags
 struct DslWs {
-  size_t pbox, S, cand, cnt, agt, tsc, acls, rows, nrows, partt, norm, pcls, pboxp, total;
+  AssignWs c;
+  size_t S, cand;
 };
 static DslWs dsl_ws(int B, int A, int nc, int M) {
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t gxc = (size_t)cdiv((long)A * ((nc + 7) / 8), 256), gxb = (size_t)cdiv(A, 256);
-  const size_t ba = (size_t)B * A;
-  DslWs w{};
-  size_t o = 0;
-  w.pbox = o; o += al(ba * 16);
-  w.S = o; o += al(ba * 4);
-  w.cand = o; o += al(ba * 4);
-  w.cnt = o; o += al(ba * 4);
-  w.agt = o; o += al(ba * 4);
-  w.tsc = o; o += al(ba * 4);
-  w.acls = o; o += al(ba * 4);
-  w.rows = o; o += al((size_t)B * (size_t)(M > 0 ? M : 1) * 4);
-  w.nrows = o; o += al((size_t)B * 4);
-  w.partt = o; o += al((size_t)B * gxb * 4);
-  w.norm = o; o += 256;
-  w.pcls = o; o += al((size_t)B * gxc * 4);
-  w.pboxp = o; o += al((size_t)B * gxb * 8);
-  w.total = o;
+  DslWs w{assign_ws(B, A, nc, M), 0, 0};
+  w.S = w.c.add((size_t)B * A * 4);
+  w.cand = w.c.add((size_t)B * A * 4);
   return w;
 }
 
@@ -513,7 +340,7 @@ extern "C" {
 
 size_t yms_dsl_loss_ws_bytes(int batch, int anchors, int nc, int n_targets) {
   if (batch <= 0 || anchors <= 0 || nc <= 0 || n_targets < 0) return 0;
-  return dsl_ws(batch, anchors, nc, n_targets).total;
+  return dsl_ws(batch, anchors, nc, n_targets).c.total;
 }
 
 yms_status yms_dsl_loss(int dtype, int batch, int nc, int nlevels, const void* const* maps, void* const* grads,
@@ -521,89 +348,42 @@ yms_status yms_dsl_loss(int dtype, int batch, int nc, int nlevels, const void* c
                         int n_targets, float img_w, float img_h, int topk, float radius, float iou_weight,
                         float beta, const float* gains, void* ws, size_t ws_bytes, float* out, int* assign_gt,
                         float* assign_score, int* dynamic_k, void* stream) {
-  if (batch <= 0 || nc <= 0 || nlevels <= 0 || nlevels > DL_MAXL || !maps || !hs || !ws_ || !strides || !out ||
-      !gains || n_targets < 0 || (n_targets > 0 && !targets))
-    return YMS_ERR_INVALID;
-  if (dtype != YMS_F32 && dtype != YMS_BF16 && dtype != YMS_F16) return YMS_ERR_INVALID;
+  if (!out || !gains || !map_dtype_ok(dtype)) return YMS_ERR_INVALID;
   if (topk < 1 || topk > DSL_TOPK || !(radius >= 0.f) || !(iou_weight >= 0.f) || !(beta >= 1.f) ||
-      !std::isfinite(radius) || !std::isfinite(iou_weight) || !std::isfinite(beta) || !(img_w > 0.f) ||
-      !(img_h > 0.f) || !std::isfinite(img_w) || !std::isfinite(img_h))
+      !std::isfinite(radius) || !std::isfinite(iou_weight) || !std::isfinite(beta))
     return YMS_ERR_INVALID;
-  if (ld < 4 * DL_DFL + nc || ld % 8) return YMS_ERR_INVALID;
-  long a_total = 0;
-  for (int l = 0; l < nlevels; ++l) {
-    if (!maps[l] || hs[l] <= 0 || ws_[l] <= 0 || !(strides[l] > 0.f) || !std::isfinite(strides[l]))
-      return YMS_ERR_INVALID;
-    if (grads && !grads[l]) return YMS_ERR_INVALID;
-    a_total += (long)hs[l] * ws_[l];
-    if (a_total >= (1l << 31)) return YMS_ERR_UNSUPPORTED;
-  }
-  if (a_total * ((nc + 7) / 8) >= (1l << 31) - 256) return YMS_ERR_UNSUPPORTED;
-  if (batch > 65535) return YMS_ERR_UNSUPPORTED;          // images are the grid's y dimension
-  LossLevels L{};
-  L.nl = nlevels;
-  L.ld = ld;
-  int A = 0;
-  for (int l = 0; l < nlevels; ++l) {
-    L.x[l] = maps[l];
-    L.g[l] = grads ? grads[l] : nullptr;
-    L.h[l] = hs[l];
-    L.w[l] = ws_[l];
-    L.stride[l] = strides[l];
-    L.off[l] = A;
-    A += hs[l] * ws_[l];
-  }
-  L.off[nlevels] = A;
+  LossLevels L;
+  int A;
+  const yms_status bad = loss_levels(batch, nc, nlevels, maps, grads, hs, ws_, strides, ld, targets, n_targets,
+                                     img_w, img_h, L, A);
+  if (bad != YMS_OK) return bad;
   const DslWs w = dsl_ws(batch, A, nc, n_targets);
-  if (!ws || ws_bytes < w.total) return YMS_ERR_INVALID;
-  char* base = (char*)ws;
-  float* pbox = (float*)(base + w.pbox);
-  float* S = (float*)(base + w.S);
-  int* cand = (int*)(base + w.cand);
-  int* cnt = (int*)(base + w.cnt);
-  int* agt = (int*)(base + w.agt);
-  float* tsc = (float*)(base + w.tsc);
-  int* acls = (int*)(base + w.acls);
-  int* rows = (int*)(base + w.rows);
-  int* nrows = (int*)(base + w.nrows);
-  float* partt = (float*)(base + w.partt);
-  float* norm = (float*)(base + w.norm);
-  float* pcls = (float*)(base + w.pcls);
-  float* pboxp = (float*)(base + w.pboxp);
-  const int gxc = cdiv((long)A * ((nc + 7) / 8), 256), gxb = cdiv(A, 256);
+  if (!ws || ws_bytes < w.c.total) return YMS_ERR_INVALID;
+  float* pbox = ws_at<float>(ws, w.c.pbox);
+  int* cnt = ws_at<int>(ws, w.c.cnt);
+  int* agt = ws_at<int>(ws, w.c.agt);
+  int* rows = ws_at<int>(ws, w.c.rows);
+  int* nrows = ws_at<int>(ws, w.c.nrows);
+  float* S = ws_at<float>(ws, w.S);
+  int* cand = ws_at<int>(ws, w.cand);
+  const int gxb = w.c.gxb, M = n_targets, B = batch;
   hipStream_t st = (hipStream_t)stream;
-  const int M = n_targets, B = batch;
   const DslParams P{radius, iou_weight, beta, topk};
-  // total = g_box box + g_cls cls + g_dfl dfl, every term a sum over norm (no factor B)
-  const float gcls = gains[1], gbox = gains[0], gdfl = gains[2] * 0.25f;
-#define YMS_DSL_CASE(T)                                                                                          \
-  if (M > 0) hipLaunchKernelGGL(dsl_rows_kernel, dim3(B), dim3(256), 0, st, targets, M, B, nc, rows, nrows);     \
-  hipLaunchKernelGGL(dsl_decode_kernel<T>, dim3(gxb, B), dim3(256), 0, st, L, targets, M, B, A, nc, img_w,       \
-                     img_h, beta, rows, nrows, pbox, S, cand, cnt, agt);                                         \
-  if (M > 0)                                                                                                     \
-    hipLaunchKernelGGL(dsl_select_kernel<T>, dim3(M), dim3(256), 0, st, L, targets, B, A, nc, img_w, img_h, P,   \
-                       pbox, S, cand, cnt, agt, dynamic_k);                                                      \
-  hipLaunchKernelGGL(dsl_resolve_kernel<T>, dim3(gxb, B), dim3(256), 0, st, L, targets, M, B, A, nc, img_w,      \
-                     img_h, P, pbox, S, cnt, rows, nrows, agt, tsc, acls, partt, assign_gt, assign_score);       \
-  hipLaunchKernelGGL(dsl_norm_kernel, dim3(1), dim3(256), 0, st, (long)B * gxb, partt, norm);                    \
-  hipLaunchKernelGGL(dsl_cls_kernel<T>, dim3(gxc, B), dim3(256), 0, st, L, A, nc, beta, tsc, acls, norm, gcls,   \
-                     pcls);                                                                                      \
-  if (grads) {                                                                                                   \
-    hipLaunchKernelGGL((dsl_box_kernel<T, true>), dim3(gxb, B), dim3(256), 0, st, L, targets, M, B, A, nc,       \
-                       img_w, img_h, agt, tsc, norm, gbox, gdfl, pboxp);                                         \
-  } else {                                                                                                       \
-    hipLaunchKernelGGL((dsl_box_kernel<T, false>), dim3(gxb, B), dim3(256), 0, st, L, targets, M, B, A, nc,      \
-                       img_w, img_h, agt, tsc, norm, gbox, gdfl, pboxp);                                         \
-  }                                                                                                              \
-  hipLaunchKernelGGL(dsl_finalize_kernel, dim3(1), dim3(256), 0, st, (long)B * gxc, pcls, (long)B * gxb, pboxp,  \
-                     norm, gains[0], gains[1], gains[2], out);
-  switch (dtype) {
-    case YMS_F32: { YMS_DSL_CASE(float) break; }
-    case YMS_BF16: { YMS_DSL_CASE(bf16) break; }
-    default: { YMS_DSL_CASE(f16) break; }
-  }
-#undef YMS_DSL_CASE
-  return launch_status();
+  return launch_for_dtype(dtype, [&](auto map_type) {
+    using T = typename decltype(map_type)::type;
+    if (M > 0) hipLaunchKernelGGL(assign_rows_kernel, dim3(B), dim3(256), 0, st, targets, M, B, nc, rows, nrows);
+    hipLaunchKernelGGL(dsl_decode_kernel<T>, dim3(gxb, B), dim3(256), 0, st, L, targets, M, B, A, nc, img_w, img_h,
+                       beta, rows, nrows, pbox, S, cand, cnt, agt);
+    if (M > 0)
+      hipLaunchKernelGGL(dsl_select_kernel<T>, dim3(M), dim3(256), 0, st, L, targets, B, A, nc, img_w, img_h, P, pbox,
+                         S, cand, cnt, agt, dynamic_k);
+    hipLaunchKernelGGL(dsl_resolve_kernel<T>, dim3(gxb, B), dim3(256), 0, st, L, targets, M, B, A, nc, img_w, img_h,
+                       P, pbox, S, cnt, rows, nrows, agt, ws_at<float>(ws, w.c.tsc), ws_at<int>(ws, w.c.acls),
+                       ws_at<float>(ws, w.c.partt), assign_gt, assign_score);
+    // total = g_box box + g_cls cls + g_dfl dfl, every term a sum over norm (no factor B); GIoU
+    assign_loss_tail<T, 1>(L, w.c, ws, targets, M, B, A, nc, img_w, img_h, DslQfl{beta}, 1.f, gains, out, out + 4,
+                           st);
+  });
 }
 
 }  // extern "C"

@@ -85,12 +85,23 @@ def _storage_elems(g):
     return B * H * W * g.stride(2) // W if g.stride(1) == 1 else g.numel()
 
 
-def det_loss(preds, targets, nc, img_size, strides=(8.0, 16.0, 32.0), iou_type="ciou", pos_weight=None,
-             lambdas=(7.5, 0.5, 1.5), need_grad=True):
-    """-> (out [4] fp32 device tensor = total, box, cls, dfl; list of gradient maps shaped like
-    ``preds`` (channels-last, same dtype) or None)."""
+class _Prepared:
+    """What the three fused losses (``det_loss``, ``tal_loss``, ``dsl_loss``) prepare alike; built by
+    ``_prepare``.  ``args``: the leading arguments their C entries share (dtype ... img_h); ``grads``: the
+    NHWC gradient buffers or None; ``B, A, M, dev``: batch, anchors, target rows, device."""
+
+    def ungrad(self):
+        """-> the gradient maps shaped like ``preds`` (padding channels dropped), or None."""
+        if self.grads is None:
+            return None
+        return [g[..., :self.C].permute(0, 3, 1, 2) for g in self.grads]
+
+
+def _prepare(what, preds, targets, nc, img_size, strides, need_grad):
+    """Checks, NHWC views with one channel stride, fp32 targets, gradient buffers and ctypes arrays
+    of one fused-loss call (``what`` names the loss in the error message)."""
     if not preds or any(p.device.type != "cuda" for p in preds):
-        raise RuntimeError("yms: the detection loss runs on ROCm GPU tensors only (no CPU fallback)")
+        raise RuntimeError(f"yms: the {what} loss runs on ROCm GPU tensors only (no CPU fallback)")
     if len(preds) > 4 or len(strides) < len(preds):
         raise ValueError("yms: 1-4 head levels with one stride each")
     dt = preds[0].dtype
@@ -113,42 +124,53 @@ def det_loss(preds, targets, nc, img_size, strides=(8.0, 16.0, 32.0), iou_type="
     M = tg.shape[0]
     hs = [p.shape[2] for p in preds]
     ws = [p.shape[3] for p in preds]
-    A = sum(h * w for h, w in zip(hs, ws))
     grads = None
     if need_grad:
         mk = torch.zeros if ld != C else torch.empty
         grads = [mk((B, h, w, ld), dtype=dt, device=dev) for h, w in zip(hs, ws)]
-    pw = None
-    if pos_weight is not None:
-        pw = torch.as_tensor(pos_weight, dtype=torch.float32, device=dev).expand(nc).contiguous()
-    wsb = L.lib().yms_det_loss_ws_bytes(B, A, nc, M)
-    ws_t = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out = torch.empty(4, dtype=torch.float32, device=dev)
     n = len(preds)
     maps = (ctypes.c_void_p * n)(*[b[0].data_ptr() for b in bases])
     gptr = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads]) if grads is not None else None
     img_h, img_w = img_size
-    L.call("yms_det_loss", L.dtype_code(dt), B, nc, n, maps, gptr, (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws),
-           (ctypes.c_float * n)(*[float(s) for s in strides[:n]]), ld, tg.data_ptr() if M else None, M,
-           ctypes.c_float(float(img_w)), ctypes.c_float(float(img_h)), IOU_TYPES[iou_type], L.ptr(pw),
+    r = _Prepared()
+    r.B, r.C, r.M, r.dev, r.grads = B, C, M, dev, grads
+    r.A = sum(h * w for h, w in zip(hs, ws))
+    r.keep = (bases, tg)                        # the buffers the pointers in args point into
+    r.args = (L.dtype_code(dt), B, nc, n, maps, gptr, (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws),
+              (ctypes.c_float * n)(*[float(s) for s in strides[:n]]), ld, tg.data_ptr() if M else None, M,
+              ctypes.c_float(float(img_w)), ctypes.c_float(float(img_h)))
+    return r
+
+
+def det_loss(preds, targets, nc, img_size, strides=(8.0, 16.0, 32.0), iou_type="ciou", pos_weight=None,
+             lambdas=(7.5, 0.5, 1.5), need_grad=True):
+    """-> (out [4] fp32 device tensor = total, box, cls, dfl; list of gradient maps shaped like
+    ``preds`` (channels-last, same dtype) or None)."""
+    p = _prepare("detection", preds, targets, nc, img_size, strides, need_grad)
+    pw = None
+    if pos_weight is not None:
+        pw = torch.as_tensor(pos_weight, dtype=torch.float32, device=p.dev).expand(nc).contiguous()
+    wsb = L.lib().yms_det_loss_ws_bytes(p.B, p.A, nc, p.M)
+    ws_t = torch.empty(wsb, dtype=torch.uint8, device=p.dev)
+    out = torch.empty(4, dtype=torch.float32, device=p.dev)
+    L.call("yms_det_loss", *p.args, IOU_TYPES[iou_type], L.ptr(pw),
            (ctypes.c_float * 3)(*[float(x) for x in lambdas]), ws_t.data_ptr(), wsb, out.data_ptr(),
-           L.stream_ptr(dev))
-    if grads is not None:
-        grads = [g[..., :C].permute(0, 3, 1, 2) for g in grads]
-    return out, grads
+           L.stream_ptr(p.dev))
+    return out, p.ungrad()
 
 
-class _DetLossFn(torch.autograd.Function):
-    """-> (total [], terms [3] = box, cls, dfl).  The kernel produces d(total)/d(maps) only, so the
-    terms are marked non-differentiable: backward through one of them raises instead of dropping it
-    (the reference returns the terms as floats, loss.py:666-672)."""
+class _FusedLossFn(torch.autograd.Function):
+    """Base of the three losses' autograd functions: -> (total [], terms [3] = box, cls, dfl).  The
+    kernels produce d(total)/d(maps) only, so the terms are marked non-differentiable: backward through
+    one of them raises instead of dropping it (the reference returns the terms as floats,
+    loss.py:666-672).  A subclass's ``forward`` is ``run`` with its loss function."""
 
     @staticmethod
-    def forward(ctx, cfg, targets, *preds):
-        out, grads = det_loss(list(preds), targets, *cfg, need_grad=any(p.requires_grad for p in preds))
+    def run(ctx, loss, cfg, targets, preds):
+        out, grads = loss(list(preds), targets, *cfg, need_grad=any(p.requires_grad for p in preds))
         ctx.grads = grads
         ctx.n_preds = len(preds)
-        terms = out[1:].clone()
+        terms = out[1:4].clone()
         ctx.mark_non_differentiable(terms)
         return out[0].clone(), terms
 
@@ -166,6 +188,18 @@ class _DetLossFn(torch.autograd.Function):
                (ctypes.c_void_p * n)(*[gr.data_ptr() for gr in grads]),
                (ctypes.c_long * n)(*[_storage_elems(gr) for gr in grads]), gf.data_ptr(), L.stream_ptr(gf.device))
         return (None, None, *grads)
+
+
+class _DetLossFn(_FusedLossFn):
+    @staticmethod
+    def forward(ctx, cfg, targets, *preds):
+        return _FusedLossFn.run(ctx, det_loss, cfg, targets, preds)
+
+
+def _loss_items(total, terms):
+    """(total [], terms [3]) -> the reference's dictionary of Python floats (one host sync)."""
+    vals = torch.cat([total.detach().view(1), terms]).cpu().tolist()
+    return {"loss_box": vals[1], "loss_cls": vals[2], "loss_dfl": vals[3], "total_loss": vals[0]}
 
 
 class ComputeLoss(nn.Module):
@@ -193,9 +227,7 @@ class ComputeLoss(nn.Module):
 
     def forward(self, preds_from_head, targets_collated):
         total, terms = self.loss_tensor(preds_from_head, targets_collated)
-        vals = torch.cat([total.detach().view(1), terms]).cpu().tolist()
-        items = {"loss_box": vals[1], "loss_cls": vals[2], "loss_dfl": vals[3], "total_loss": vals[0]}
-        return total, items
+        return total, _loss_items(total, terms)
 
     def loss_tensor(self, preds_from_head, targets_collated):
         """-> (total [] device tensor, differentiable; terms [3] device tensor (box, cls, dfl), not

@@ -36,7 +36,7 @@ import torch
 from torch import nn
 
 from yms import _lib as L
-from yolov8.tools.loss import DFL_CH, _nhwc, _storage_elems
+from yolov8.tools.loss import _FusedLossFn, _loss_items, _prepare
 
 
 def tal_loss(preds, targets, nc, img_size, strides=(8.0, 16.0, 32.0), topk=10, alpha=0.5, beta=6.0,
@@ -45,86 +45,28 @@ def tal_loss(preds, targets, nc, img_size, strides=(8.0, 16.0, 32.0), topk=10, a
     ``preds`` (channels-last, same dtype) or None) and, ``return_assignment``, a third element
     (assign_gt [B, A] int32: target row or -1, assign_score [B, A] fp32: t(a)); anchors level-major,
     then row-major.  No host sync."""
-    if not preds or any(p.device.type != "cuda" for p in preds):
-        raise RuntimeError("yms: the task-aligned loss runs on ROCm GPU tensors only (no CPU fallback)")
-    if len(preds) > 4 or len(strides) < len(preds):
-        raise ValueError("yms: 1-4 head levels with one stride each")
     if not 1 <= int(topk) <= 10:
         raise ValueError("yms: topk must be in 1..10")
-    dt = preds[0].dtype
-    B = preds[0].shape[0]
-    C = 4 * DFL_CH + nc
-    for p in preds:
-        if p.dim() != 4 or p.shape[0] != B or p.shape[1] != C or p.dtype != dt:
-            raise ValueError(f"yms: head maps must be [B, {C}, H, W] of one dtype, got {tuple(p.shape)} {p.dtype}")
-    bases = [_nhwc(p) for p in preds]
-    ld = bases[0][1]
-    if any(b[1] != ld for b in bases):          # one channel stride for every level: repack
-        ld = (C + 7) // 8 * 8
-        bases = []
-        for p in preds:
-            t = torch.zeros((B, p.shape[2], p.shape[3], ld), dtype=dt, device=p.device)
-            t[..., :C] = p.permute(0, 2, 3, 1)
-            bases.append((t, ld))
-    dev = preds[0].device
-    tg = targets.to(device=dev, dtype=torch.float32).reshape(-1, 6).contiguous()
-    M = tg.shape[0]
-    hs = [p.shape[2] for p in preds]
-    ws = [p.shape[3] for p in preds]
-    A = sum(h * w for h, w in zip(hs, ws))
-    grads = None
-    if need_grad:
-        mk = torch.zeros if ld != C else torch.empty
-        grads = [mk((B, h, w, ld), dtype=dt, device=dev) for h, w in zip(hs, ws)]
+    p = _prepare("task-aligned", preds, targets, nc, img_size, strides, need_grad)
     agt = asc = None
     if return_assignment:
-        agt = torch.empty((B, A), dtype=torch.int32, device=dev)
-        asc = torch.empty((B, A), dtype=torch.float32, device=dev)
-    wsb = L.lib().yms_tal_loss_ws_bytes(B, A, nc, M)
-    ws_t = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out = torch.empty(4, dtype=torch.float32, device=dev)
-    n = len(preds)
-    maps = (ctypes.c_void_p * n)(*[b[0].data_ptr() for b in bases])
-    gptr = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads]) if grads is not None else None
-    img_h, img_w = img_size
-    L.call("yms_tal_loss", L.dtype_code(dt), B, nc, n, maps, gptr, (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws),
-           (ctypes.c_float * n)(*[float(s) for s in strides[:n]]), ld, tg.data_ptr() if M else None, M,
-           ctypes.c_float(float(img_w)), ctypes.c_float(float(img_h)), int(topk), ctypes.c_float(float(alpha)),
-           ctypes.c_float(float(beta)), (ctypes.c_float * 3)(*[float(x) for x in lambdas]), ws_t.data_ptr(), wsb,
-           out.data_ptr(), L.ptr(agt), L.ptr(asc), L.stream_ptr(dev))
-    if grads is not None:
-        grads = [g[..., :C].permute(0, 3, 1, 2) for g in grads]
+        agt = torch.empty((p.B, p.A), dtype=torch.int32, device=p.dev)
+        asc = torch.empty((p.B, p.A), dtype=torch.float32, device=p.dev)
+    wsb = L.lib().yms_tal_loss_ws_bytes(p.B, p.A, nc, p.M)
+    ws_t = torch.empty(wsb, dtype=torch.uint8, device=p.dev)
+    out = torch.empty(4, dtype=torch.float32, device=p.dev)
+    L.call("yms_tal_loss", *p.args, int(topk), ctypes.c_float(float(alpha)), ctypes.c_float(float(beta)),
+           (ctypes.c_float * 3)(*[float(x) for x in lambdas]), ws_t.data_ptr(), wsb, out.data_ptr(), L.ptr(agt),
+           L.ptr(asc), L.stream_ptr(p.dev))
     if return_assignment:
-        return out, grads, (agt, asc)
-    return out, grads
+        return out, p.ungrad(), (agt, asc)
+    return out, p.ungrad()
 
 
-class _TalLossFn(torch.autograd.Function):
-    """-> (total [], terms [3] = box, cls, dfl).  The kernels produce d(total)/d(maps) only, so the
-    terms are marked non-differentiable, as in ``yolov8.tools.loss._DetLossFn``."""
-
+class _TalLossFn(_FusedLossFn):
     @staticmethod
     def forward(ctx, cfg, targets, *preds):
-        out, grads = tal_loss(list(preds), targets, *cfg, need_grad=any(p.requires_grad for p in preds))
-        ctx.grads = grads
-        ctx.n_preds = len(preds)
-        terms = out[1:].clone()
-        ctx.mark_non_differentiable(terms)
-        return out[0].clone(), terms
-
-    @staticmethod
-    def backward(ctx, g, _gterms):
-        grads = ctx.grads
-        ctx.grads = None
-        if grads is None:
-            return (None, None) + (None,) * ctx.n_preds
-        # grads *= g in place on the device (a no-op launch for the 1.0 seed of loss.backward())
-        gf = g.detach().to(torch.float32).contiguous()
-        n = len(grads)
-        L.call("yms_scale_by_device_scalar", L.dtype_code(grads[0].dtype), n,
-               (ctypes.c_void_p * n)(*[gr.data_ptr() for gr in grads]),
-               (ctypes.c_long * n)(*[_storage_elems(gr) for gr in grads]), gf.data_ptr(), L.stream_ptr(gf.device))
-        return (None, None, *grads)
+        return _FusedLossFn.run(ctx, tal_loss, cfg, targets, preds)
 
 
 class TaskAlignedLoss(nn.Module):
@@ -148,9 +90,7 @@ class TaskAlignedLoss(nn.Module):
 
     def forward(self, preds_from_head, targets_collated):
         total, terms = self.loss_tensor(preds_from_head, targets_collated)
-        vals = torch.cat([total.detach().view(1), terms]).cpu().tolist()
-        items = {"loss_box": vals[1], "loss_cls": vals[2], "loss_dfl": vals[3], "total_loss": vals[0]}
-        return total, items
+        return total, _loss_items(total, terms)
 
     def loss_tensor(self, preds_from_head, targets_collated):
         """-> (total [] device tensor, differentiable; terms [3] device tensor (box, cls, dfl), not
