@@ -247,6 +247,30 @@ yms_status yms_bn_act_bwd_reduce_finalize(int dtype, long npix, int c, const voi
  * counter as above). */
 yms_status yms_bias_bwd(int dtype, long npix, int c, const void* gy, int gy_ld, int gy_off,
                         float* ws, unsigned* counter, float* dbias, void* stream);
+/* Backward of y = act(z*scale + shift) (+res) where scale / shift fold the RUNNING statistics (a
+ * BatchNorm2d in eval mode inside a training step), in ONE launch: gy and z are read once,
+ *   da = gy * act'(z*scale + shift), dz = scale * da (dz may alias z), gres as yms_bn_act_bwd_apply;
+ *   dbeta = sum da, dgamma = sum da * (z - mean) * invstd with mean_invstd = (running_mean, invstd),
+ * summed like yms_bn_act_bwd_reduce_finalize (ws: yms_bn_bwd_rows rows; *counter 0 on entry and on
+ * exit; deterministic).  dgamma and dbeta both NULL: a plain streaming pass; mean_invstd, ws and
+ * counter are then unused and may be NULL. */
+yms_status yms_bn_frozen_act_bwd(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
+                                 const void* gy, int gy_ld, int gy_off, const float* scale,
+                                 const float* shift, const float* mean_invstd, int act, void* dz, int dz_ld,
+                                 int dz_off, void* gres, int gres_ld, int gres_off, int gres_acc, float* ws,
+                                 unsigned* counter, float* dgamma, float* dbeta, void* stream);
+/* yms_bn_fold plus the table that backward reads: mean_invstd[0][i] = rmean[i], mean_invstd[1][i] =
+ * 1/sqrt(rvar[i] + eps), the rows mi_ld floats apart (>= c).  scale / shift are yms_bn_fold's bits.
+ * Batched: njobs layers in one launch from a DEVICE table; scale, shift and mean_invstd are byte
+ * offsets from base; max_c >= every job's c. */
+typedef struct {
+  const float* gamma; const float* beta; const float* rmean; const float* rvar;
+  float eps; int c, mi_ld;
+  long scale, shift, mean_invstd;
+} yms_bn_fold_job;
+yms_status yms_bn_fold_mi(int c, const float* gamma, const float* beta, const float* rmean, const float* rvar,
+                          float eps, float* scale, float* shift, float* mean_invstd, int mi_ld, void* stream);
+yms_status yms_bn_fold_mi_batched(int njobs, const yms_bn_fold_job* jobs_dev, int max_c, void* base, void* stream);
 /* Grouped forms of the passes above: njobs INDEPENDENT jobs (host array, each the arguments of the solo
  * call), up to eight per launch.  Every member keeps its solo launch's block count and per-block
  * pixel ranges / partial rows, so all outputs are bit-identical to njobs solo calls.  A job alone in

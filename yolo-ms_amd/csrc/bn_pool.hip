@@ -39,6 +39,28 @@ __global__ void bn_fold_kernel(int c, const float* g, const float* b, const floa
   shift[i] = b[i] - rm[i] * sc;
 }
 
+// The fold of a BatchNorm2d in eval mode inside a TRAINING step: scale / shift exactly as bn_fold_kernel
+// (so the layer's forward is bit-identical to the eval plan's), plus the (running_mean, invstd) table
+// the BN backward passes read in place of the batch statistics.  One job per layer, blockIdx.y = job;
+// the outputs are byte offsets from `base` (the step's arena), so one device table serves every step.
+struct FoldJob {
+  const float *g, *b, *rm, *rv;
+  float eps;
+  int c, mi_ld;
+  long scale, shift, mi;
+};
+__global__ void bn_fold_mi_kernel(const FoldJob* jobs, const FoldJob solo, char* base) {   // jobs NULL: solo, base 0
+  const FoldJob j = jobs ? jobs[blockIdx.y] : solo;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= j.c) return;
+  const float sc = j.g[i] / sqrtf(j.rv[i] + j.eps);
+  reinterpret_cast<float*>(base + j.scale)[i] = sc;
+  reinterpret_cast<float*>(base + j.shift)[i] = j.b[i] - j.rm[i] * sc;
+  float* mi = reinterpret_cast<float*>(base + j.mi);
+  mi[i] = j.rm[i];
+  mi[j.mi_ld + i] = 1.0f / sqrtf(j.rv[i] + j.eps);
+}
+
 // Statistics rows (conv_common.hpp contract): row r = (sum z, sum (z - mean_r)^2) over n_r
 // pixels, n_r = counts[r] (the producers write the count table right after the rows; rows with
 // n_r = 0 are skipped).  Rows are merged in ONE pass in fp64 with the shifted-data form of
@@ -428,6 +450,97 @@ struct BwdFin {          // fused finalize (FIN): the last reduce block to finis
   long count;
 };
 
+// The tail the partial-row kernels share.  block_rows_store: a block's per-thread sums -> its partial row
+// [2][c] of ws.  last_block_finish: the in-launch finalize over the nblk rows.
+__device__ __forceinline__ void block_rows_store(const ChanMap& m, int c, int c0, const float (&a1)[8],
+                                                 const float (&a2)[8], float (&red)[2][2048 + 64], float* ws,
+                                                 const long row) {
+  // reduce over the PY pixel lanes in a fixed order: red[k][py*8G + g*8 + i]
+  const int W = m.G * 8;
+  for (int lane0 = 0; lane0 < m.PY; lane0 += 2048 / W) {
+    const int lanes = min(m.PY - lane0, 2048 / W);
+    if (m.active && m.py >= lane0 && m.py < lane0 + lanes) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        red[0][(m.py - lane0) * W + c0 + i] = a1[i];
+        red[1][(m.py - lane0) * W + c0 + i] = a2[i];
+      }
+    }
+    __syncthreads();
+    for (int ch = threadIdx.x; ch < c; ch += 256) {
+      float t1 = 0.f, t2 = 0.f;
+      for (int l = 0; l < lanes; ++l) { t1 += red[0][l * W + ch]; t2 += red[1][l * W + ch]; }
+      if (lane0 == 0) {
+        ws[row * 2 * c + ch] = t1;          // row = the block's pixel range
+        ws[row * 2 * c + c + ch] = t2;
+      } else {
+        ws[row * 2 * c + ch] += t1;
+        ws[row * 2 * c + c + ch] += t2;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ void last_block_finish(int c, const float* ws, float (&red)[2][2048 + 64],
+                                                  const BwdFin& fin, const unsigned nblk) {
+  // in-launch finalize (cdna_hip_programming.md G16 counter hand-off): every wave drains its
+  // partial-row stores, one agent-scope release + ticket; the block drawing the last ticket
+  // acquires and sums all rows in a fixed order (deterministic whichever block is last)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  unsigned* flag = reinterpret_cast<unsigned*>(&red[0][0]);
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(fin.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned last = (t == nblk - 1) ? 1u : 0u;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    flag[0] = last;
+  }
+  __syncthreads();
+  if (flag[0] == 0) return;
+  __syncthreads();
+  const int rows = nblk, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  double* dred = reinterpret_cast<double*>(&red[0][0]);     // [2][8][33] doubles
+  for (int cb = 0; cb < c; cb += 32) {
+    const int ch = cb + tx;
+    double b1[4] = {0, 0, 0, 0}, b2[4] = {0, 0, 0, 0};
+    if (ch < c) {
+      int r = ty;
+      for (; r + 24 < rows; r += 32) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          b1[u] += ws[(long)(r + 8 * u) * 2 * c + ch];
+          b2[u] += ws[(long)(r + 8 * u) * 2 * c + c + ch];
+        }
+      }
+      for (; r < rows; r += 8) {
+        b1[0] += ws[(long)r * 2 * c + ch];
+        b2[0] += ws[(long)r * 2 * c + c + ch];
+      }
+    }
+    dred[(0 * 8 + ty) * 33 + tx] = (b1[0] + b1[1]) + (b1[2] + b1[3]);
+    dred[(1 * 8 + ty) * 33 + tx] = (b2[0] + b2[1]) + (b2[2] + b2[3]);
+    __syncthreads();
+    if (ty == 0 && ch < c) {
+      double t1 = 0.0, t2 = 0.0;
+      for (int k = 0; k < 8; ++k) { t1 += dred[(0 * 8 + k) * 33 + tx]; t2 += dred[(1 * 8 + k) * 33 + tx]; }
+      if (fin.dbeta) fin.dbeta[ch] = (float)t1;
+      if (fin.dgamma) fin.dgamma[ch] = (float)t2;
+      if (fin.coef) {
+        fin.coef[ch] = (float)(t1 / (double)fin.count);
+        fin.coef[c + ch] = (float)(t2 / (double)fin.count);
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(fin.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // PIPE = false: the serial loop for every c (c % 8 != 0 tails; the host launches PIPE = true)
 template <typename T, bool HAS_Z, bool FIN, bool PIPE>
 __device__ __forceinline__ void bn_bwd_reduce_body(long npix, int c, const T* z, int z_ld, int z_off, const T* gy,
@@ -516,88 +629,8 @@ __device__ __forceinline__ void bn_bwd_reduce_body(long npix, int c, const T* z,
       }
     }
   }
-  // reduce over the PY pixel lanes in a fixed order: red[k][py*8G + g*8 + i]
-  const int W = m.G * 8;
-  for (int lane0 = 0; lane0 < m.PY; lane0 += 2048 / W) {
-    const int lanes = min(m.PY - lane0, 2048 / W);
-    if (m.active && m.py >= lane0 && m.py < lane0 + lanes) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        red[0][(m.py - lane0) * W + c0 + i] = a1[i];
-        red[1][(m.py - lane0) * W + c0 + i] = a2[i];
-      }
-    }
-    __syncthreads();
-    for (int ch = threadIdx.x; ch < c; ch += 256) {
-      float t1 = 0.f, t2 = 0.f;
-      for (int l = 0; l < lanes; ++l) { t1 += red[0][l * W + ch]; t2 += red[1][l * W + ch]; }
-      if (lane0 == 0) {
-        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + ch] = t1;          // row = the block's pixel range
-        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + c + ch] = t2;
-      } else {
-        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + ch] += t1;
-        ws[block_range<BN_REV_RED>(bid, nblk) * 2 * c + c + ch] += t2;
-      }
-    }
-    __syncthreads();
-  }
-  if constexpr (FIN) {
-    // in-launch finalize (cdna_hip_programming.md G16 counter hand-off): every wave drains its
-    // partial-row stores, one agent-scope release + ticket; the block drawing the last ticket
-    // acquires and sums all rows in a fixed order (deterministic whichever block is last)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned* flag = reinterpret_cast<unsigned*>(&red[0][0]);
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned t = __hip_atomic_fetch_add(fin.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned last = (t == nblk - 1) ? 1u : 0u;
-      if (last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      flag[0] = last;
-    }
-    __syncthreads();
-    if (flag[0] == 0) return;
-    __syncthreads();
-    const int rows = nblk, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    double* dred = reinterpret_cast<double*>(&red[0][0]);     // [2][8][33] doubles
-    for (int cb = 0; cb < c; cb += 32) {
-      const int ch = cb + tx;
-      double b1[4] = {0, 0, 0, 0}, b2[4] = {0, 0, 0, 0};
-      if (ch < c) {
-        int r = ty;
-        for (; r + 24 < rows; r += 32) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            b1[u] += ws[(long)(r + 8 * u) * 2 * c + ch];
-            b2[u] += ws[(long)(r + 8 * u) * 2 * c + c + ch];
-          }
-        }
-        for (; r < rows; r += 8) {
-          b1[0] += ws[(long)r * 2 * c + ch];
-          b2[0] += ws[(long)r * 2 * c + c + ch];
-        }
-      }
-      dred[(0 * 8 + ty) * 33 + tx] = (b1[0] + b1[1]) + (b1[2] + b1[3]);
-      dred[(1 * 8 + ty) * 33 + tx] = (b2[0] + b2[1]) + (b2[2] + b2[3]);
-      __syncthreads();
-      if (ty == 0 && ch < c) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int k = 0; k < 8; ++k) { t1 += dred[(0 * 8 + k) * 33 + tx]; t2 += dred[(1 * 8 + k) * 33 + tx]; }
-        if (fin.dbeta) fin.dbeta[ch] = (float)t1;
-        if (fin.dgamma) fin.dgamma[ch] = (float)t2;
-        if (fin.coef) {
-          fin.coef[ch] = (float)(t1 / (double)fin.count);
-          fin.coef[c + ch] = (float)(t2 / (double)fin.count);
-        }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) __hip_atomic_store(fin.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  block_rows_store(m, c, c0, a1, a2, red, ws, block_range<BN_REV_RED>(bid, nblk));
+  if constexpr (FIN) last_block_finish(c, ws, red, fin, nblk);
 }
 template <typename T, bool HAS_Z, bool FIN = false, bool PIPE = true>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(long npix, int c, const T* z, int z_ld,
@@ -815,6 +848,124 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(BnGroup<PassJob
   bn_bwd_apply_body<T, PIPE>(j.npix, j.c, (const T*)j.z, j.z_ld, j.z_off, (const T*)j.gy, j.gy_ld, j.gy_off, j.scale,
                              j.shift, j.mi, j.coef, j.act, (T*)j.out, j.out_ld, j.out_off, (T*)j.res, j.res_ld,
                              j.res_off, j.res_acc, j.ppb, bid, nblk);
+}
+
+// ------------------------------------------------------------------------------------------
+// BN with RUNNING statistics (a BatchNorm2d in eval mode inside a training step) + act, backward in
+// ONE pass.  The normalisation is a fixed per-channel affine map, so dz needs no batch sums:
+//   da = gy * act'(z*scale + shift),  dz = scale * da  (over z, in place, or elsewhere),
+//   gres = gy or gres += gy,  and, SUMS, dbeta = sum da, dgamma = sum da * (z - running_mean) * invstd
+// through the partial rows and the in-launch finalize of the reduce above.  gy and z are read once
+// (two reads + one write per element, against the three passes' four reads + one write).
+// The loop is the apply pass's: every pixel is loaded, summed and stored by ONE thread, the next
+// group's loads go out before this group's stores, and a clamped duplicate (another thread's pixel,
+// perhaps already overwritten by its dz) is masked out of the sums and the stores alike.
+// ------------------------------------------------------------------------------------------
+template <typename T, bool SUMS>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const PassJob j, const BwdFin fin) {
+  ChanMap m(j.c);
+  const int c = j.c, c0 = m.g * 8, nv = min(8, c - c0);
+  const T *z = (const T*)j.z, *gy = (const T*)j.gy;
+  T *dz = (T*)j.out, *gres = (T*)j.res;
+  float a1[8], a2[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { a1[i] = 0.f; a2[i] = 0.f; }
+  if (m.active) {
+    float sc[8], sh[8], mu[8], is[8];
+    load_params8(j.scale, c0, c, sc, 0.f);
+    load_params8(j.shift, c0, c, sh, 0.f);
+    if (SUMS) {
+      load_params8(j.mi, c0, c, mu, 0.f);
+      load_params8(j.mi + c, c0, c, is, 0.f);
+    }
+    const long p0 = (long)blockIdx.x * j.ppb, p1 = min(j.npix, p0 + j.ppb);
+    const int act = j.act;
+    const bool racc = gres && j.res_acc;
+    auto emit = [&](long pix, const Raw8<T>& g, const Raw8<T>& zz, const Raw8<T>& rres, int valid) {
+      float gv[8], zv[8], out[8];
+      unpack8(g, gv);
+      unpack8(zz, zv);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float da = gv[i];
+        if (act == YMS_ACT_SILU) da *= dsilu_f(zv[i] * sc[i] + sh[i]);
+        out[i] = sc[i] * da;
+        if (SUMS) {
+          a1[i] += da;
+          a2[i] += da * ((zv[i] - mu[i]) * is[i]);
+        }
+      }
+      if (gres) {
+        if (racc) {
+          float r[8];
+          unpack8(rres, r);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) r[i] += gv[i];
+          store8(gres + pix * j.res_ld + j.res_off + c0, valid, r);
+        } else {
+          store8(gres + pix * j.res_ld + j.res_off + c0, valid, gv);
+        }
+      }
+      store8(dz + pix * j.out_ld + j.out_off + c0, valid, out);
+    };
+    const long step = (long)m.PY * BN_UA;
+    if (c % 8 == 0) {
+      auto issue = [&](long b, Raw8<T> (&g)[BN_UA], Raw8<T> (&zz)[BN_UA], Raw8<T> (&rres)[BN_UA]) {
+#pragma unroll
+        for (int u = 0; u < BN_UA; ++u) {
+          const long pix = min(b + (long)u * m.PY, p1 - 1);
+          load_raw8(gy + pix * j.gy_ld + j.gy_off + c0, 8, g[u]);
+          load_raw8(z + pix * j.z_ld + j.z_off + c0, 8, zz[u]);
+          if (racc) load_raw8(gres + pix * j.res_ld + j.res_off + c0, 8, rres[u]);
+        }
+      };
+      auto consume = [&](long b, const Raw8<T> (&g)[BN_UA], const Raw8<T> (&zz)[BN_UA], const Raw8<T> (&rres)[BN_UA]) {
+#pragma unroll
+        for (int u = 0; u < BN_UA; ++u) {
+          const long pix = b + (long)u * m.PY;
+          if (pix < p1) emit(pix, g[u], zz[u], rres[u], 8);
+        }
+      };
+      long base = p0 + m.py;
+      if (base < p1) {
+        Raw8<T> ga[BN_UA], za[BN_UA], ra[BN_UA], gb[BN_UA], zb[BN_UA], rb[BN_UA];
+        issue(base, ga, za, ra);
+        while (true) {
+          issue(base + step, gb, zb, rb);
+          consume(base, ga, za, ra);
+          base += step;
+          if (base >= p1) break;
+          issue(base + step, ga, za, ra);
+          consume(base, gb, zb, rb);
+          base += step;
+          if (base >= p1) break;
+        }
+      }
+    } else {
+      for (long base = p0 + m.py; base < p1; base += step) {
+        Raw8<T> gr[BN_UA], zr[BN_UA], rr[BN_UA];
+#pragma unroll
+        for (int u = 0; u < BN_UA; ++u) {
+          const long pix = base + (long)u * m.PY;
+          if (pix < p1) {
+            load_raw8(gy + pix * j.gy_ld + j.gy_off + c0, nv, gr[u]);
+            load_raw8(z + pix * j.z_ld + j.z_off + c0, nv, zr[u]);
+            if (racc) load_raw8(gres + pix * j.res_ld + j.res_off + c0, nv, rr[u]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < BN_UA; ++u) {
+          const long pix = base + (long)u * m.PY;
+          if (pix < p1) emit(pix, gr[u], zr[u], rr[u], nv);
+        }
+      }
+    }
+  }
+  if constexpr (SUMS) {
+    __shared__ float red[2][2048 + 64];
+    block_rows_store(m, c, c0, a1, a2, red, j.ws, (long)blockIdx.x);
+    last_block_finish(c, j.ws, red, fin, gridDim.x);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1721,6 +1872,52 @@ yms_status yms_bn_act_bwd_apply_group(int dtype, int njobs, const yms_bn_pass_jo
 }
 yms_status yms_bias_bwd_group(int dtype, int njobs, const yms_bn_pass_job* jobs, void* stream) {
   return run_pass<BiasPass>(dtype, njobs, jobs, stream);
+}
+
+// With sums the blocks are the two-kernel reduce's (one partial row each: yms_bn_bwd_rows rows, the
+// bound of ws); without, the apply pass's (a plain streaming pass, no ws, no counter).
+yms_status yms_bn_frozen_act_bwd(int dtype, long npix, int c, const void* z, int z_ld, int z_off,
+                                 const void* gy, int gy_ld, int gy_off, const float* scale,
+                                 const float* shift, const float* mean_invstd, int act, void* dz, int dz_ld,
+                                 int dz_off, void* gres, int gres_ld, int gres_off, int gres_acc, float* ws,
+                                 unsigned* counter, float* dgamma, float* dbeta, void* stream) {
+  const yms_bn_pass_job j{npix, c, z, z_ld, z_off, gy, gy_ld, gy_off, scale, shift, mean_invstd, nullptr, act,
+                          dz, dz_ld, dz_off, gres, gres_ld, gres_off, gres_acc, ws, counter, dbeta};
+  const bool sums = dgamma || dbeta;
+  if (npix <= 0 || !z || !gy || !dz || !scale || !shift) return YMS_ERR_INVALID;
+  if (!vok(z_ld, z_off, c) || !vok(gy_ld, gy_off, c) || !vok(dz_ld, dz_off, c)) return YMS_ERR_INVALID;
+  if (gres && !vok(gres_ld, gres_off, c)) return YMS_ERR_INVALID;
+  if (sums && (!mean_invstd || !ws || !counter)) return YMS_ERR_INVALID;
+  if (c > 2048) return YMS_ERR_UNSUPPORTED;
+  const long ppb = sums ? reduce_ppb(j) : apply_ppb(j);
+  const PassJob pj = pass_job(j, ppb);
+  const BwdFin fin{counter, dgamma, dbeta, nullptr, npix};
+  const dim3 grid(pix_blocks(npix, ppb));
+  hipStream_t st = (hipStream_t)stream;
+  if (sums) YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_frozen_bwd_kernel<T, true>), grid, dim3(256), 0, st, pj, fin));
+  else YMS_DT_DISPATCH(dtype, T, hipLaunchKernelGGL((bn_frozen_bwd_kernel<T, false>), grid, dim3(256), 0, st, pj, fin));
+  return launch_status();
+}
+
+// yms_bn_fold plus the [2][mi_ld] (running_mean, invstd) table; the batched form runs njobs layers'
+// folds in one launch from a DEVICE table of yms_bn_fold_job whose outputs are byte offsets from base.
+yms_status yms_bn_fold_mi(int c, const float* gamma, const float* beta, const float* rmean, const float* rvar,
+                          float eps, float* scale, float* shift, float* mean_invstd, int mi_ld, void* stream) {
+  if (c <= 0 || !gamma || !beta || !rmean || !rvar || !scale || !shift || !mean_invstd || mi_ld < c)
+    return YMS_ERR_INVALID;
+  const FoldJob j{gamma, beta, rmean, rvar, eps, c, mi_ld, (long)(intptr_t)scale, (long)(intptr_t)shift,
+                  (long)(intptr_t)mean_invstd};
+  hipLaunchKernelGGL(bn_fold_mi_kernel, dim3(cdiv(c, 256)), dim3(256), 0, (hipStream_t)stream, nullptr, j, nullptr);
+  return launch_status();
+}
+
+yms_status yms_bn_fold_mi_batched(int njobs, const yms_bn_fold_job* jobs_dev, int max_c, void* base, void* stream) {
+  static_assert(sizeof(yms_bn_fold_job) == sizeof(FoldJob), "yms_bn_fold_job is FoldJob");
+  if (njobs < 0 || max_c <= 0 || (njobs > 0 && (!jobs_dev || !base))) return YMS_ERR_INVALID;
+  if (njobs == 0) return YMS_OK;
+  hipLaunchKernelGGL(bn_fold_mi_kernel, dim3(cdiv(max_c, 256), njobs), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const FoldJob*>(jobs_dev), FoldJob{}, (char*)base);
+  return launch_status();
 }
 
 size_t yms_sppf_ws_bytes(int n, int h, int w, int c) {

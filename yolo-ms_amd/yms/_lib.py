@@ -75,6 +75,10 @@ class BnPassJob(ctypes.Structure):
                        "act:i out:p out_ld:i out_off:i res:p res_ld:i res_off:i res_acc:i ws:p counter:p dbias:p")
 
 
+class BnFoldJob(ctypes.Structure):
+    _fields_ = _fields("gamma:p beta:p rmean:p rvar:p eps:f c:i mi_ld:i scale:l shift:l mean_invstd:l")
+
+
 class BnBwdFinalizeJob(ctypes.Structure):
     _fields_ = _fields("c:i ws:p rows:i count:l dgamma:p dbeta:p coef:p")
 
@@ -160,6 +164,10 @@ _SIGS = {
     "yms_bn_act_bwd_reduce_finalize": (_I, [_I, _L, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P,
                                             _P, _P]),
     "yms_bias_bwd": (_I, [_I, _L, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "yms_bn_frozen_act_bwd": (_I, [_I, _L, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _I, _I, _I,
+                                   _P, _P, _P, _P, _P]),
+    "yms_bn_fold_mi": (_I, [_I, _P, _P, _P, _P, _F, _P, _P, _P, _I, _P]),
+    "yms_bn_fold_mi_batched": (_I, [_I, _P, _I, _P, _P]),
     "yms_bn_finalize_group": (_I, [_I, _P, _P]),
     "yms_affine_act_group": (_I, [_I, _I, _P, _P]),
     "yms_bn_act_bwd_reduce_group": (_I, [_I, _I, _P, _P]),
@@ -295,6 +303,8 @@ _ARGS = {k: v.split() for k, v in {
     "yms_bn_act_bwd_apply": "dtype npix c z z_ld z_off gy gy_ld gy_off scale shift mean_invstd coef act "
                             "out out_ld out_off res res_ld res_off res_acc",
     "yms_bias_bwd": "dtype npix c gy gy_ld gy_off ws counter dbias",
+    "yms_bn_frozen_act_bwd": "dtype npix c z z_ld z_off gy gy_ld gy_off scale shift mean_invstd act "
+                             "out out_ld out_off res res_ld res_off res_acc ws counter",     # + dgamma, dbeta
 }.items()}
 _JOB_ARGS = {k: operator.attrgetter(*[f for f in v if f != "dtype"]) for k, v in _ARGS.items()}
 
@@ -348,7 +358,7 @@ def _work_job(name, j, dtype):
         return 0, 2 * vol                                          # z, gy
     if name == "yms_affine_act":
         return 0, (2 + (j.res is not None)) * vol                  # z (+res) -> y
-    if name == "yms_bn_act_bwd_apply":
+    if name in ("yms_bn_act_bwd_apply", "yms_bn_frozen_act_bwd"):
         return 0, (3 + (j.res is not None) * (1 + bool(j.res_acc))) * vol   # z, gy -> dz (+ gres)
     return 0, 0
 

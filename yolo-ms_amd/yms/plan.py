@@ -64,6 +64,11 @@ class Options:
     # YMS_HEAD_GROUP: the head's independent levels run stage by stage as grouped launches (HeadGroup):
     # 0 off, 1 the forward only, 2 forward and backward
     head_group: int
+    # YMS_BWD_SKIP=0: every op runs its backward, whatever its parameters and inputs need (Plan._find_backward)
+    bwd_skip: bool
+    # YMS_BN_FROZEN=0: the backward of an eval-mode BatchNorm as the three batch-statistics passes (running
+    # statistics as mean_invstd, a zeroed coefficient table) instead of yms_bn_frozen_act_bwd
+    bn_frozen: bool
     # the library's process-wide direct-conv route (yms_conv_direct_set): it changes
     # yms_conv_stats_rows and yms_conv_dgrad_bnred_rows, which size the plan's scratch
     direct: int
@@ -79,7 +84,8 @@ def read_options():
         raise RuntimeError(f"yms: YMS_HEAD_GROUP={hg!r}: expected 0 (off), 1 (forward) or 2 (forward + backward)")
     return Options(stem=on("YMS_STEM"), head_fuse=on("YMS_HEAD_FUSE"), bnred=on("YMS_BNRED"),
                    wgrad_tail_first=on("YMS_WGRAD_FIRST"), grad_inplace=on("YMS_GRAD_INPLACE"),
-                   wgrad_stream=on("YMS_WGRAD_STREAM"), head_group=int(hg), direct=L.lib().yms_conv_direct_set(-1))
+                   wgrad_stream=on("YMS_WGRAD_STREAM"), head_group=int(hg), bwd_skip=on("YMS_BWD_SKIP"),
+                   bn_frozen=on("YMS_BN_FROZEN"), direct=L.lib().yms_conv_direct_set(-1))
 
 
 class Buf:
@@ -269,6 +275,10 @@ class Rt:
 class Op:
     """What a plan asks of every op besides fwd / bwd / plan_grads; the default answer is nothing."""
     flops = 0
+    # set per plan by Plan._find_backward
+    runs_bwd = True     # the backward walk runs this op (a parameter of its own or an input needs a gradient)
+    bn_eval = False     # its BatchNorm modules are in eval mode inside a training plan: running statistics
+    infer = False       # bn_eval and no backward: the conv's epilogue writes y, there is no z
 
     def layout(self, plan, La, Le):
         pass
@@ -313,11 +323,12 @@ class ConvBase(Op):
 
     def layout_packs(self, plan, La):
         self.t_wp = La.alloc(self.wp_elems * plan.es)
-        self.t_wpt = La.alloc(self.wpt_elems * plan.es)
+        self.t_wpt = La.alloc(self.wpt_elems * plan.es) if self.runs_bwd else None
 
     def pack_specs(self):
+        # (the transposed pack serves the input gradient: an op without a backward has none)
         w = self.conv.weight.data_ptr()
-        return [(self.sp, w, self.t_wp, 0), (self.sp, w, self.t_wpt, 1)]
+        return [(self.sp, w, self.t_wp, 0)] + ([(self.sp, w, self.t_wpt, 1)] if self.runs_bwd else [])
 
     def prepare_eval(self, rt):
         L.call("yms_conv_pack_weight", self.sp, self.conv.weight.data_ptr(), rt.eval_base + self.e_wp, 0, rt.st)
@@ -395,24 +406,30 @@ class BNConvBase(ConvBase):
         statistics tables (one per part), the BN backward and the weight gradient (wg_ws) need."""
         c = self.c
         self.zld = r8(c)
-        self.z = La.alloc(self.npix * self.zld * plan.es)
+        self.z = None if self.infer else La.alloc(self.npix * self.zld * plan.es)
         self.layout_packs(plan, La)
         self.sc = La.alloc(4 * c)
         self.sh = La.alloc(4 * c)
         self.mi = La.alloc(8 * c)
-        for m, _ in self.parts():
-            plan.need_scratch("stats", 4 * m.stats_rows * (2 * m.stats_ld + 1))
         self.bwd_rows = L.lib().yms_bn_bwd_rows(self.npix, c)
+        if not self.bn_eval:
+            for m, _ in self.parts():
+                plan.need_scratch("stats", 4 * m.stats_rows * (2 * m.stats_ld + 1))
+        if not self.runs_bwd:
+            return
         plan.need_scratch("bwd", 4 * 2 * c * self.bwd_rows)
         plan.need_scratch("coef", 8 * c)
         plan.need_scratch("wgrad", self.wg_ws)
+        if self.bn_eval:
+            plan.need_scratch("zcoef", 8 * c)      # the three-pass route's all-zero coefficients
+            self.fz_cnt = plan.counter()           # the one-pass route's arrival counter
 
     def z_padding(self, es):
         # z buffers with padding channels (c % 8 != 0, e.g. a head with nc = 3): the convs and the BN
         # apply (dz written over z) touch only the c real channels, while the input gradient reads
         # the whole 16-B groups -- padding left as arena garbage (NaN / Inf bit patterns) times the
         # zero weight rows is NaN, so those z buffers start zeroed and their padding stays zero
-        return [(self.z, self.npix * self.zld * es)] if self.zld != self.c else []
+        return [(self.z, self.npix * self.zld * es)] if self.zld != self.c and self.z is not None else []
 
     # ---- job records (include/yms.h) of this op's passes: its own fwd / bwd call the solo entry points
     # with them, a HeadGroup collects its members' into grouped calls.  grp: as a member of a group, in the
@@ -424,12 +441,36 @@ class BNConvBase(ConvBase):
             eb = rt.eval_base
             return [(m, (rt.a(m.y), m.y.buf.ld, m.y.off, eb + m.e_sc, eb + m.e_sh, m.act, m.res, None))
                     for m, _ in self.parts()]
+        if self.infer:      # eval-mode BN, no backward: as the eval plan, with this step's folded scale / shift
+            sc, sh = rt.base + self.sc, rt.base + self.sh
+            return [(m, (rt.a(m.y), m.y.buf.ld, m.y.off, sc + 4 * off, sh + 4 * off, m.act, m.res, None))
+                    for m, off in self.parts()]
         z, st = rt.base + self.z, rt.base + rt.plan.scratch["stats"]
-        return [(m, (z, self.zld, off, None, None, L.ACT_NONE, None, st + (m.g_stats if grp else 0)))
+        return [(m, (z, self.zld, off, None, None, L.ACT_NONE, None,
+                     None if self.bn_eval else st + (m.g_stats if grp else 0)))
                 for m, off in self.parts()]
+
+    def fold_jobs(self):
+        """Eval-mode BN: per part, the fold of its running statistics into this op's scale / shift /
+        (running_mean, invstd) slots -- Plan.prepack runs them all in one launch per step."""
+        return [L.BnFoldJob(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                            bn.running_var.data_ptr(), bn.eps, m.c, self.c, self.sc + 4 * off, self.sh + 4 * off,
+                            self.mi + 4 * off)
+                for m, off in (self.parts() if self.bn_eval else ()) for bn in (m.mod.bn,)]
+
+    def fold_own(self, rt):
+        """The solo folds, on rt.st: without the batched prepack, and always for a stem -- the runner issues
+        the prepack on the side stream and runs the stem's forward on the main stream before joining the
+        two, so the stem's coefficients must not come from the side stream (Plan.fold_table leaves it out)."""
+        if not rt.prepacked or self.stem_input is not None:
+            for j in self.fold_jobs():
+                L.call("yms_bn_fold_mi", j.c, j.gamma, j.beta, j.rmean, j.rvar, ctypes.c_float(j.eps),
+                       rt.base + j.scale, rt.base + j.shift, rt.base + j.mean_invstd, j.mi_ld, rt.st)
 
     def finalize_jobs(self, rt, grp=False):
         """Per part, into its channel slot of this op's state (mean / invstd rows are self.c apart)."""
+        if self.bn_eval:
+            return []
         st, sc, sh, mi = (rt.base + o for o in (rt.plan.scratch["stats"], self.sc, self.sh, self.mi))
         return [L.BnFinalizeJob(m.c, st + (m.g_stats if grp else 0), m.stats_rows, m.stats_ld, self.npix,
                                 bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
@@ -457,9 +498,14 @@ class BNConvBase(ConvBase):
         ws, rows = gb + gs["bwd"] + (self.g_bwd if grp else 0), self.bwd_rows
         if self.bnred_by is not None:
             ws, rows = gb + gs[self.bnred_key], self.bnred_rows
+        fcoef = coef
+        if self.bn_eval:
+            # running statistics: dz = scale * (da - 0 - xhat * 0), so the finalize writes no coefficients
+            # and the apply reads a table of zeros
+            fcoef, coef = None, gb + gs["zcoef"]
         gy = dict(gy=rt.g(y), gy_ld=y.buf.ld, gy_off=y.off, mean_invstd=rt.base + self.mi)
         res, res_ld, res_off = _opt(rt.g, self.res)
-        return (self.pass_job(rt, ws=ws, **gy), L.BnBwdFinalizeJob(self.c, ws, rows, self.npix, dg, db, coef),
+        return (self.pass_job(rt, ws=ws, **gy), L.BnBwdFinalizeJob(self.c, ws, rows, self.npix, dg, db, fcoef),
                 self.pass_job(rt, coef=coef, out=rt.base + self.z, out_ld=self.zld, out_off=0, res=res, res_ld=res_ld,
                               res_off=res_off, res_acc=self.acc_res, **gy))
 
@@ -477,12 +523,32 @@ class BNConvBase(ConvBase):
             m.conv_fwd(rt, *args)
             if fins:
                 L.call_job("yms_bn_finalize" if m is self else "yms_bn_finalize_ld", fins[i], rt.st)
-        if fins:
+        if rt.training and not self.infer:
             L.call_job("yms_affine_act", self.affine_job(rt), rt.st, rt.plan.dt)
+
+    def one_pass(self, sums):
+        """Eval-mode BN: does yms_bn_frozen_act_bwd serve this layer's backward?  Always as a plain streaming
+        pass (1.8-2.1x the three passes); with dgamma / dbeta wanted, its last block sums the rows * 2c partial
+        table alone, which pays where that table is small (the fused reduce's bound) or the tensor large:
+        (25600, 256) measured 47 us against the three passes' 41, the four other layer shapes 1.2-1.45x
+        faster (profiles/bn_frozen_bwd_micro.txt)."""
+        return not sums or self.bwd_rows * self.c <= 32768 or self.npix * self.c >= 1 << 23
+
+    def frozen_bwd(self, rt, dg, db):
+        """Eval-mode BN: the whole BN + act backward as one launch -> dz."""
+        y, gb, gs = self.y, rt.gbase, rt.plan.gscratch
+        res, res_ld, res_off = _opt(rt.g, self.res)
+        job = self.pass_job(rt, gy=rt.g(y), gy_ld=y.buf.ld, gy_off=y.off, mean_invstd=rt.base + self.mi,
+                            out=rt.base + self.z, out_ld=self.zld, out_off=0, res=res, res_ld=res_ld, res_off=res_off,
+                            res_acc=self.acc_res, ws=gb + gs["bwd"], counter=rt.cnt(self.fz_cnt))
+        L.call("yms_bn_frozen_act_bwd", *L.job_args("yms_bn_frozen_act_bwd", job, rt.plan.dt), dg, db, rt.st)
+        return self.dz(rt)
 
     def bn_bwd(self, rt, dg, db):
         """The reduce (unless bnred_by) and finalize passes -> the apply record, for bn_bwd_apply."""
         red, fin, app = self.bwd_jobs(rt, dg, db)
+        if self.bn_eval and dg is None and db is None:
+            return app          # running statistics, gamma and beta frozen: nothing to sum, the apply alone gives dz
         if self.bnred_by is None:
             L.call_job("yms_bn_act_bwd_reduce", red, rt.st, rt.plan.dt)
         L.call_job("yms_bn_act_bwd_finalize", fin, rt.st)
@@ -547,6 +613,7 @@ class ConvOp(BNConvBase):
     def fwd(self, rt):
         if rt.training:
             self.pack_unless_prepacked(rt)
+            self.fold_own(rt)
         super().fwd(rt)
 
     def conv_fwd(self, rt, out, ld, off, sc, sh, act, res, stats):
@@ -565,7 +632,11 @@ class ConvOp(BNConvBase):
                q.zld, 0, base + q.sc, base + q.sh, base + q.mi, q.act, rt.gbase + rt.plan.gscratch[self.bnred_wkey], rt.st)
 
     def bwd(self, rt):
-        app = self.bn_bwd(rt, *self.bn_grads(rt))
+        dg, db = self.bn_grads(rt)
+        if (self.bn_eval and self.stem_input is None and rt.plan.opts.bn_frozen
+                and self.one_pass(dg is not None or db is not None)):
+            return self.bwd_grads(rt, *self.frozen_bwd(rt, dg, db), self.tail_wgrad_first)
+        app = self.bn_bwd(rt, dg, db)
         if self.stem_input is not None:
             # the stem's input needs no gradient: the apply pass is fused into the weight
             # gradient, which reads gy, z and the NCHW input.
@@ -640,10 +711,12 @@ class SiblingConvOp(BNConvBase):
     def layout_packs(self, plan, La):
         for m in self.members:
             m.t_wp = La.alloc(m.wp_elems * plan.es)
-        self.t_wpt = La.alloc(self.wpt_elems * plan.es)
+        self.t_wpt = La.alloc(self.wpt_elems * plan.es) if self.runs_bwd else None
 
     def pack_specs(self):
         specs = [(m.sp, m.mod.conv.weight.data_ptr(), m.t_wp, 0) for m in self.members]
+        if not self.runs_bwd:
+            return specs
         a, bb = self.members
         specs.append((self.sp, a.mod.conv.weight.data_ptr(), self.t_wpt, 1,
                       (bb.mod.conv.weight.data_ptr(), a.c)))
@@ -679,6 +752,8 @@ class SiblingConvOp(BNConvBase):
         dg, db = self.bn_grads(rt)
         if dg is not None and db is not None:
             app = self.bn_bwd(rt, dg, db)
+        elif self.bn_eval and all(rt.pgrad(pi) is None for m in self.members for pi in (m.pg, m.pb)):
+            app = self.bn_bwd(rt, None, None)
         else:
             tmp = rt.gbase + rt.plan.gscratch["sib"]
             app = self.bn_bwd(rt, tmp, tmp + 4 * c)
@@ -902,6 +977,15 @@ def _op_views(op):
                 yield from _op_views(u)
 
 
+def _in_views(op):
+    """The Views an op reads: all it holds but its output (SppfPoolOp.v is both)."""
+    for k, v in vars(op).items():
+        if k not in ("y", "members"):
+            for u in (v if isinstance(v, (list, tuple)) else (v,)):
+                if isinstance(u, View):
+                    yield u
+
+
 def _array(jobs):
     return (type(jobs[0]) * len(jobs))(*jobs)
 
@@ -967,7 +1051,8 @@ class HeadGroup:
                     continue
                 for m, _ in op.parts():
                     m.g_stats = stats
-                    stats += _al(4 * m.stats_rows * (2 * m.stats_ld + 1))
+                    if not op.bn_eval:           # (running statistics: no table)
+                        stats += _al(4 * m.stats_rows * (2 * m.stats_ld + 1))
                 op.g_bwd, op.g_coef = bwd, coef
                 bwd += _al(4 * 2 * op.c * op.bwd_rows)
                 coef += _al(8 * op.c)
@@ -987,10 +1072,11 @@ class HeadGroup:
     def fwd_stage(self, rt, st):
         convs = [m.conv_job(rt, *args) for op in st for m, args in op.conv_args(rt, True)]
         L.call("yms_conv_fwd_group", len(convs), _array(convs), rt.st)
-        bn = [op for op in st if rt.training and isinstance(op, BNConvBase)]
-        if bn:
-            fins = [j for op in bn for j in op.finalize_jobs(rt, True)]
+        bn = [op for op in st if rt.training and isinstance(op, BNConvBase) and not op.infer]
+        fins = [j for op in bn for j in op.finalize_jobs(rt, True)]
+        if fins:
             L.call("yms_bn_finalize_group", len(fins), _array(fins), rt.st)
+        if bn:
             L.call("yms_affine_act_group", rt.plan.dt, len(bn), _array([op.affine_job(rt) for op in bn]), rt.st)
 
     # ---- backward ------------------------------------------------------------------------
@@ -998,7 +1084,7 @@ class HeadGroup:
         """The grouped backward serves the case every training step meets: all the members' parameters
         take a gradient and each sibling pair's gradients are adjacent in the flat arena.  Otherwise
         (a frozen member), and with Options.head_group < 2, the members run their own backward."""
-        if rt.plan.opts.head_group < 2:
+        if rt.plan.opts.head_group < 2 or not all(op.runs_bwd for op in self.ops):
             return False
         for op in self.ops:
             if any(rt.pgrad(pi) is None for pi in op.grad_params()):
@@ -1010,7 +1096,8 @@ class HeadGroup:
     def bwd(self, rt):
         if not self.bwd_grouped(rt):
             for op in self.bwd_ops:
-                op.bwd(rt)
+                if op.runs_bwd:
+                    op.bwd(rt)
             return
         for st in reversed(self.stages):
             self.bwd_stage(rt, st[::-1])
@@ -1082,12 +1169,13 @@ class Builder:
     def sibling_convs(self, mods, x):
         """Two Conv blocks reading the same input x -> their output views, the channel slots of one
         buffer (SiblingConvOp), or two separate ConvOps when they cannot share one (different
-        geometry or activation, a first member whose width is not a multiple of 8, or
-        YMS_HEAD_FUSE=0)."""
+        geometry or activation, a first member whose width is not a multiple of 8, BatchNorm modules
+        in different modes -- one in eval mode inside a training plan, the other not: the fused BN
+        passes take one kind of statistics -- or YMS_HEAD_FUSE=0)."""
         ks = {(m.conv.kernel_size, m.conv.stride, m.conv.padding, m.conv.groups, m.conv.dilation,
                isinstance(m.activation, torch.nn.SiLU)) for m in mods}
         fuse = (len(mods) == 2 and len(ks) == 1 and mods[0].conv.groups == 1 and mods[0].conv.out_channels % 8 == 0
-                and self.opts.head_fuse)
+                and self.opts.head_fuse and (not self.training or len({m.bn.training for m in mods}) == 1))
         if not fuse:
             return [m.emit(self, x) for m in mods]
         conv = mods[0].conv
@@ -1145,7 +1233,11 @@ class Plan:
         self._pg_layouts = {}       # requires_grad pattern -> flat parameter-gradient arena layout
         self._infer_arenas = {}     # (stream, host thread) -> a decode plan's internal arena
         self._nbt = None            # the BatchNorm num_batches_tracked tensors a training step bumps
+        self._fold_tables = {}      # parameter set -> the eval-mode BN folds' device job table (fold_table)
+        self._fold_bns = self._fold_now = None
+        self.root = getattr(b, "root", None)    # the module the plan was built from (names in messages)
         self.stem_inputs = self._find_stems()
+        self._find_backward()
         if self.training and self.opts.wgrad_tail_first:
             stem_out = {op.y.buf.idx for op in self.stem_inputs.values()}
             for op in self.ops:
@@ -1153,6 +1245,8 @@ class Plan:
                     op.tail_wgrad_first = True
         self._find_bnred()
         self.groups = self._find_groups(b.chain_sets)
+        # the backward walk: the steps that have anything to run, in reverse
+        self.bwd_sched = [s for s in reversed(self.sched) if any(op.runs_bwd for op in getattr(s, "ops", (s,)))]
         La, Le = Layout(), Layout()
         # an input the stem conv reads as NCHW fp32 has no NHWC buffer: no arena bytes, and no
         # per-step zeroing of its padding channels (3 -> 8: 419 MB, 51 us per configs[2] step)
@@ -1177,6 +1271,8 @@ class Plan:
         self.gscratch = {k: Lg.alloc(self.scratch_req.get(k, 0)) for k in ("bwd", "coef", "wgrad", "sppf", "stemwg", "sib")}
         for k in sorted(k for k in self.scratch_req if k.startswith("bnr")):
             self.gscratch[k] = Lg.alloc(self.scratch_req[k])
+        if "zcoef" in self.scratch_req:
+            self.gscratch["zcoef"] = Lg.alloc(self.scratch_req["zcoef"])
         self.gscratch["cnt"] = Lg.alloc(16 * max(self.n_counters, 1))
         self.garena_bytes = Lg.size
         self.eval_bytes = Le.size
@@ -1188,7 +1284,10 @@ class Plan:
             self.seed_acc = [T.write(v) for v in self.outputs]
             T.writes = set()
             for op in reversed(self.ops):
-                op.plan_grads(T)
+                # only the ops that run write or read a gradient: a skipped producer never reads its slot of
+                # a buffer whose other slots' consumers wrote the whole of it (the neck's concat buffers)
+                if op.runs_bwd:
+                    op.plan_grads(T)
                 y = getattr(op, "y", None)
                 if isinstance(y, View) and not any(y is o for o in self.outputs):
                     _check_not_in_place(op, y)
@@ -1198,6 +1297,8 @@ class Plan:
             self.grad_read_only = {v.buf.idx for v in self.outputs if v.buf.idx not in T.writes}
             self.gzero_ranges = [(bf.off, bf.npix * bf.ld * self.es) for bf in self.bufs if bf.idx in T.zero]
             self.gzero_ranges.append((self.gscratch["cnt"], 16 * max(self.n_counters, 1)))
+            if "zcoef" in self.gscratch:
+                self.gzero_ranges.append((self.gscratch["zcoef"], self.scratch_req["zcoef"]))
         self.flops = sum(op.flops for op in self.ops)
         # parameter-gradient arena in backward-completion order (reverse op order)
         order = []
@@ -1232,6 +1333,56 @@ class Plan:
                 out[i] = op
         return out
 
+    def _name(self, mod):
+        names = [n for n, m in self.root.named_modules() if m is mod] if self.root is not None else []
+        return names[0] if names else type(mod).__name__
+
+    def _find_backward(self):
+        """Which ops run a backward, which buffers need a gradient, which BN layers use running statistics.
+        Static per plan: runner.get_plan keys the cache by the parameters' requires_grad pattern and the
+        BatchNorm modules' train / eval pattern.
+
+        An op runs its backward iff a parameter of its own requires a gradient or one of its inputs needs
+        one; a buffer needs a gradient iff the producer of any of its slots runs its backward, or it is a
+        plan input that requires one (set by get_plan).  An op that does not run launches nothing in the
+        backward; one that runs with an input that needs no gradient skips its input gradient
+        (x.buf.needs_grad, as the plan inputs always did).  YMS_BWD_SKIP=0: everything runs.
+
+        A BatchNorm module in eval mode inside a training plan normalises with its running statistics
+        and leaves them alone (bn_eval); where nothing downstream of it needs a backward either, the op
+        takes the inference route (infer: the conv's epilogue writes y, no z)."""
+        for op in self.ops:
+            op.runs_bwd, op.bn_eval, op.infer = True, False, False
+        if not self.training:
+            return
+        req = [getattr(m, a).requires_grad for m, a in self.param_refs]
+        skip = self.opts.bwd_skip
+        if skip:
+            ins = {v.buf.idx for v in self.inputs}
+            for bf in self.bufs:
+                if bf.idx not in ins:
+                    bf.needs_grad = False
+        for op in self.ops:
+            if skip:
+                op.runs_bwd = (any(req[pi] for pi in op.grad_params())
+                               or any(v.buf.needs_grad for v in _in_views(op)))
+                if op.runs_bwd and isinstance(getattr(op, "y", None), View):
+                    op.y.buf.needs_grad = True
+            ev = [not m.bn.training for m in op.bn_modules()]
+            if any(ev) and not all(ev):
+                raise RuntimeError("yms: " + " and ".join(self._name(m) for m in op.bn_modules()) + " run as one fused "
+                                   "pass over both outputs, so their BatchNorm modules must be in the same mode "
+                                   "(both train or both eval), or set YMS_HEAD_FUSE=0")
+            op.bn_eval = any(ev)
+            for m in op.bn_modules() if op.bn_eval else ():
+                if m.bn.running_mean is None or m.bn.running_var is None:
+                    raise RuntimeError(f"yms: {self._name(m)}.bn is in eval mode without running statistics "
+                                       "(track_running_stats=False): torch would normalise with batch statistics "
+                                       "there, which the running-statistics routes do not do")
+            op.infer = op.bn_eval and skip and not op.runs_bwd
+            for m in getattr(op, "members", ()):
+                m.runs_bwd, m.bn_eval, m.infer = op.runs_bwd, op.bn_eval, op.infer
+
     def _find_bnred(self):
         """Training, 16-bit: a Conv whose input gradient runs on the direct 3x3 kernel
         (yms_conv_dgrad_bnred_rows > 0) and whose input view is exactly the output of an earlier
@@ -1251,7 +1402,7 @@ class Plan:
 
         n = 0
         for i, c in enumerate(self.ops):
-            if type(c) is not ConvOp or c.stem_input is not None or not c.x.buf.needs_grad:
+            if type(c) is not ConvOp or c.stem_input is not None or not c.x.buf.needs_grad or not c.runs_bwd:
                 continue
             rows = L.lib().yms_conv_dgrad_bnred_rows(c.sp)
             if rows <= 0:
@@ -1263,7 +1414,7 @@ class Plan:
                 continue
             q = self.ops[j]
             if (type(q) is not ConvOp or q.y.off != x.off or q.y.c != x.c or q.c != x.c or q.bnred_by is not None
-                    or q.act not in (L.ACT_NONE, L.ACT_SILU)):
+                    or q.act not in (L.ACT_NONE, L.ACT_SILU) or not q.runs_bwd or q.bn_eval):
                 continue
             if any(_overlap(v, x) for op in self.ops[j + 1:i] for v in views(op)):
                 continue
@@ -1346,6 +1497,26 @@ class Plan:
             if len(cache) >= 4:
                 cache.clear()
             ent = cache[key] = (table, len(jobs), singles)
+        self._fold_now = self.fold_table()      # (uploaded on the current stream too; prepack uses this one)
+        return ent
+
+    def fold_table(self):
+        """(device table, jobs, widest c) of the eval-mode BN layers' folds, cached like pack_table (the
+        table holds parameter addresses and arena offsets); None without such layers."""
+        if self._fold_bns is None:      # once per plan: the layers (a stem folds itself, BNConvBase.fold_own)
+            ops = [op for op in self.ops if op.bn_eval and op.stem_input is None]
+            self._fold_ops, self._fold_bns = ops, [m.mod.bn for op in ops for m, _ in op.parts()]
+        if not self._fold_bns:
+            return None
+        key = tuple([t.data_ptr() for bn in self._fold_bns for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)])
+        ent = self._fold_tables.get(key)
+        if ent is None:
+            jobs = [j for op in self._fold_ops for j in op.fold_jobs()]
+            host = torch.frombuffer(bytearray(bytes(_array(jobs))), dtype=torch.uint8)
+            table = host.to(torch.device("cuda", torch.cuda.current_device()))
+            if len(self._fold_tables) >= 4:
+                self._fold_tables.clear()
+            ent = self._fold_tables[key] = (table, len(jobs), max(j.c for j in jobs))
         return ent
 
     def prepack(self, rt, ent=None):
@@ -1357,6 +1528,9 @@ class Plan:
         L.call("yms_conv_pack_weights_batched", nj, table.data_ptr(), rt.base, rt.st)
         for sp, w, dst, fd in singles:
             L.call("yms_conv_pack_weight", sp, w, rt.base + dst, fd, rt.st)
+        fold = self._fold_now           # (pack_table's, of this step)
+        if fold is not None:
+            L.call("yms_bn_fold_mi_batched", fold[1], fold[0].data_ptr(), fold[2], rt.base, rt.st)
         rt.prepacked = True
 
     def new_arena(self, device, stream):

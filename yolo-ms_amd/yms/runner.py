@@ -47,9 +47,29 @@ def _check_inputs(inputs):
                                "(move the model and inputs to 'cuda'); there is no CPU fallback")
 
 
+_STATE_ATTR = "_yms_train_state"
+
+
+def train_state(module):
+    """(requires_grad of every parameter, training of every BatchNorm module) below `module`: what a
+    training plan's backward skip and BN routes are decided from (Plan._find_backward), hence part of
+    its cache key.  The module tree is walked once; a call reads one flag per parameter and BN module
+    through the modules' own dicts (so a parameter replaced by load_state_dict(assign=True) is seen),
+    about as much host work as the plan.params() every step does anyway."""
+    src = module.__dict__.get(_STATE_ATTR)
+    if src is None:
+        mods = list(module.modules())
+        src = module.__dict__[_STATE_ATTR] = (
+            [(m._parameters, n) for m in mods for n, p in m._parameters.items() if p is not None],
+            [m for m in mods if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)])
+    ps, bns = src
+    return tuple([d[n].requires_grad for d, n in ps]), tuple([m.training for m in bns])
+
+
 def get_plan(module, inputs, dt, training):
     opts = read_options()
-    key = (tuple(tuple(x.shape) for x in inputs), tuple(bool(x.requires_grad) for x in inputs), dt, training, opts)
+    key = (tuple(tuple(x.shape) for x in inputs), tuple(bool(x.requires_grad) for x in inputs), dt, training, opts,
+           train_state(module) if training else None)
     cache = module.__dict__.setdefault(_CACHE_ATTR, {})
     plan = cache.get(key)
     if plan is None:
@@ -57,6 +77,7 @@ def get_plan(module, inputs, dt, training):
             if x.dim() != 4:
                 raise RuntimeError(f"yms: expected NCHW 4-D input, got shape {tuple(x.shape)}")
         b = Builder(inputs[0].shape[0], L.dtype_code(dt), training, opts)
+        b.root = module
         in_views, outs, kind = module._yms_plan(b, inputs)
         for v, x in zip(in_views, inputs):
             v.buf.name = "input"
@@ -141,6 +162,33 @@ def _side_stream(dev):
 L_DTYPES = {L.F32: torch.float32, L.BF16: torch.bfloat16, L.F16: torch.float16}
 
 
+def _run_forward(plan, rt, main, side):
+    """The training forward's launches: the step's packs and folds, then the ops.  main / side: the
+    current stream and the weight-gradient side stream (None: everything on rt.st)."""
+    ops = plan.sched
+    if side is not None and plan.ops and plan.ops[0] in plan.stem_inputs.values():
+        # the stem conv reads the fp32 weight itself (and folds an eval-mode BN itself, on the main
+        # stream): the step's weight packs go to the side stream and overlap it; every later conv is
+        # ordered after them
+        stream = rt.st
+        ent = plan.pack_table()          # a first-call table upload goes on main, before the wait
+        side.wait_stream(main)
+        rt.st = side.cuda_stream
+        plan.prepack(rt, ent)
+        rt.st = stream
+        ops[0].fwd(rt)
+        # main joins the side stream right here, so any later reuse of the arena's or the
+        # table's memory (main-stream ordered) comes after the packs: no record_stream (which
+        # would defer the arena's reuse and, with the host steps ahead, make the caching
+        # allocator map a second ~100 GB arena for YOLO-MS-L)
+        main.wait_stream(side)
+        ops = ops[1:]
+    else:
+        plan.prepack(rt)
+    for op in ops:
+        op.fwd(rt)
+
+
 class _PlanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, state, *args):
@@ -151,27 +199,8 @@ class _PlanFn(torch.autograd.Function):
         arena = plan.new_arena(dev, stream)
         rt = Rt(plan, arena.data_ptr(), stream, True)
         _load_inputs(plan, rt, inputs)
-        ops = plan.sched
-        if plan.opts.wgrad_stream and plan.ops and plan.ops[0] in plan.stem_inputs.values():
-            # the stem conv reads the fp32 weight itself: the step's weight packs go to the side
-            # stream and overlap it; every later conv is ordered after them
-            main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-            ent = plan.pack_table()          # a first-call table upload goes on main, before the wait
-            side.wait_stream(main)
-            rt.st = side.cuda_stream
-            plan.prepack(rt, ent)
-            rt.st = stream
-            ops[0].fwd(rt)
-            # main joins the side stream right here, so any later reuse of the arena's or the
-            # table's memory (main-stream ordered) comes after the packs: no record_stream (which
-            # would defer the arena's reuse and, with the host steps ahead, make the caching
-            # allocator map a second ~100 GB arena for YOLO-MS-L)
-            main.wait_stream(side)
-            ops = ops[1:]
-        else:
-            plan.prepack(rt)
-        for op in ops:
-            op.fwd(rt)
+        side = _side_stream(dev) if plan.opts.wgrad_stream and plan.stem_inputs else None
+        _run_forward(plan, rt, torch.cuda.current_stream(dev), side)
         state.arena = arena
         state.rt = rt
         state.in_meta = [(x.shape, x.dtype, x.requires_grad) for x in inputs]
@@ -235,7 +264,7 @@ class _PlanFn(torch.autograd.Function):
         if hook is not None:
             views = param_views()
             hook.begin(plan, pg, ptrs, views)
-        for step in reversed(plan.sched):
+        for step in plan.bwd_sched:      # (the steps with anything to run: Plan._find_backward)
             step.bwd(rt)
             # (a HeadGroup finishes all its member ops together: their buckets go out after it)
             for op in getattr(step, "bwd_ops", (step,)):
@@ -324,10 +353,10 @@ def run(module, inputs, grad_hook=None):
 
 
 def _bump_bn_counters(plan):
-    """nn.BatchNorm2d increments num_batches_tracked in training forward."""
+    """nn.BatchNorm2d increments num_batches_tracked in training forward (a module in eval mode does not)."""
     ts = plan._nbt
     if ts is None:
-        ts = plan._nbt = [m.bn.num_batches_tracked for op in plan.ops for m in op.bn_modules()]
+        ts = plan._nbt = [m.bn.num_batches_tracked for op in plan.ops if not op.bn_eval for m in op.bn_modules()]
     if ts:
         with torch.no_grad():
             torch._foreach_add_(ts, 1)

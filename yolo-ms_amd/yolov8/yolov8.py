@@ -14,6 +14,7 @@ from yolov8.model.yolov8_backbone import Backbone
 from yolov8.model.yolov8_neck import Neck
 from yolov8.model.yolov8_head import Head
 from yolov8.model.yolo_ms import MSBackbone, MSNeck, is_ms_version
+from yms import finetune as _finetune
 from yms import runner as _runner
 
 
@@ -44,6 +45,12 @@ class YOLOv8(nn.Module):
         f = nk.emit(b, p3, p4, p5, cats=cats)
         outs = self.head.emit(b, *f)
         return [xin], outs, ("maps" if b.training else ("decode", self.head))
+
+    def train(self, mode: bool = True):
+        # the BN modules yms.finetune put into eval mode stay there (nothing recorded: nothing changes)
+        super().train(mode)
+        _finetune.reapply(self)
+        return self
 
     def forward(self, x):
         _, outs = _runner.run(self, [x])
