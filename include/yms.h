@@ -30,6 +30,8 @@
  *   yms_augment_normalize
  *   yms_mosaic_normalize    the config's `mosaic` / `mixup` keys, which dataset.py never reads:
  *                           YOLOv5 load_mosaic / random_perspective / mixup semantics, opt-in
+ *   yms_box_targets         the boxes of those samples (dataset.py:84-88, :218-228 filters) from a device
+ *                           annotation table, for the device-resident loader (yms.cache), opt-in
  *   yms_optim_*             tools/utils.py:11-25 get_optimizer's torch.optim.SGD / Adam step, plus the
  *                           weight EMA, clip_grad_norm_ and non-finite guard (train.py:365,376), opt-in
  */
@@ -477,6 +479,22 @@ yms_status yms_augment_normalize(int dtype, int n, const void* images, int out_h
 size_t yms_mosaic_image_bytes(void);
 yms_status yms_mosaic_normalize(int dtype, int n, const void* records, int out_h, int out_w, const float* mean,
                                 const float* std, void* out, void* stream);
+/* The targets of a batch of sampled plans (yms.data.transform_boxes / mosaic_boxes restated in
+ * float64, operation order in csrc/targets.hip), for a loader whose images and annotations stay on
+ * the device (yms.cache), opt-in.  boxes / labels: device annotation table, float64 [nann][4] COCO
+ * xywh and int32 [nann].  layers: device array of nlayers records (yms_tgt_layer_bytes() each):
+ * { int nst, out_w, out_h, pad; double m[8][9] } -- the FORWARD 3x3 stage maps and the output frame.
+ * tiles: device array of ntiles records (yms_tgt_tile_bytes() each), sorted by out0:
+ * { int image, layer, ann0, count, out0, clip; double gx, gy, ox, oy, rx0, ry0, rx1, ry1 } -- the
+ * tile's `count` boxes are annotation rows ann0.., its results are output rows out0..; a box maps to
+ * the canvas as (ox + x gx, oy + y gy) and, when clip != 0, is intersected with the rect.
+ * out: fp32 [m_cap][6], m_cap = the sum of the counts; EVERY row is written: (image, class, cx, cy, w,
+ * h) for a box that survives the filters, (-1, 0, 0, 0, 0, 0) otherwise -- a row the losses ignore.
+ * m_cap == 0: YMS_OK, nothing launched. */
+size_t yms_tgt_tile_bytes(void);
+size_t yms_tgt_layer_bytes(void);
+yms_status yms_box_targets(int ntiles, const void* tiles, int nlayers, const void* layers, const double* boxes,
+                           const int* labels, long nann, int m_cap, float* out, void* stream);
 
 /* ---- detection loss ------------------------------------------------------- */
 /* The reference's ComputeLoss (yolov8/tools/loss.py:94-677; python binding

@@ -209,6 +209,9 @@ _SIGS = {
     "yms_augment_normalize": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "yms_mosaic_image_bytes": (_SZ, []),
     "yms_mosaic_normalize": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "yms_tgt_tile_bytes": (_SZ, []),
+    "yms_tgt_layer_bytes": (_SZ, []),
+    "yms_box_targets": (_I, [_I, _P, _I, _P, _P, _P, _L, _I, _P, _P]),
     "yms_det_loss": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _P, _P, _P, _SZ, _P, _P]),
     "yms_scale_by_device_scalar": (_I, [_I, _I, _P, _P, _P, _P]),
     "yms_tal_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),
