@@ -26,6 +26,8 @@
  *   yms_det_*               nothing in the reference: the COCO evaluation protocol (multi-label
  *                           candidates, max_nms / max_det caps, letterbox unmap) around
  *                           yms_nms_classwise, opt-in
+ *   yms_tta_merge,          nothing in the reference: test-time augmentation's view merge and box
+ *   yms_det_finalize_vote   voting around the same detect, opt-in
  *   yms_resize_normalize,   tools/dataset.py:84-134 transform list + collate_fn's stack (:260)
  *   yms_augment_normalize
  *   yms_mosaic_normalize    the config's `mosaic` / `mixup` keys, which dataset.py never reads:
@@ -616,6 +618,56 @@ yms_status yms_det_finalize(int n, int K, int max_det, const float* cand_boxes, 
                             const int* true_label, const int* cand_anchor, const int64_t* keep_idx,
                             const int* counts, const float* frames, float* det, int* det_anchor, int* det_count,
                             void* stream);
+
+/* ---- test-time augmentation: view merge in front of yms_det_candidates, box voting behind the NMS ---- */
+/* Nothing in the reference.  The multi-view protocols of the published numbers (ultralytics
+ * augment=True: scales 1 / 0.83 / 0.67 with a left-right flip on the middle view; the RTMDet-lineage
+ * tta_model: 3 sizes x flip) de-flip and de-scale every view's predictions, concatenate them and run
+ * one NMS; ultralytics' merge=True then replaces each kept box by the score-weighted mean of the boxes
+ * around it.  Semantics and tie rules are this package's (parity with ultralytics / mmyolo UNPINNED).
+ *
+ * yms_tta_merge: nviews in 1..YMS_TTA_MAX_VIEWS decoded predictions preds[v] [n, A[v], 4+nc] fp32
+ * (yms_head_decode's out; boxes (cx, cy, w, h) in view pixels) -> out [n, R, 4+nc], R = sum of
+ * a1[v] - a0[v]: view v's rows [a0[v], a1[v]) in call order, ascending inside a view (merged row
+ * roff_v + (a - a0[v]) with roff_v the prefix sum of the earlier views' row counts).  H[v] x W[v] is the
+ * view's input size, flips[v] bit 0 = the input was flipped left-right, bit 1 = up-down
+ * (yms_resize_normalize's bits), frames[v] device fp32 [n][6] = (gain_x, gain_y, pad_x, pad_y, w0,
+ * h0) of the view's letterbox per image.  Per row, each operation separately rounded in fp32:
+ *   x = (flip & 1) ? (float)W - cx : cx;   y = (flip & 2) ? (float)H - cy : cy;
+ *   cx0 = (x - pad_x) / gain_x;  cy0 = (y - pad_y) / gain_y;  w0 = w / gain_x;  h0 = h / gain_y
+ * Nothing is clipped; the nc scores are copied bit for bit (a NaN keeps its payload); a NaN or
+ * infinite box number or a zero gain propagates by IEEE rules.  The arrays preds, A, a0, a1, H, W,
+ * flips and frames are HOST arrays of nviews entries, read during the call (they travel as kernel
+ * arguments: no device table).  One launch, no host read of device memory, no allocation:
+ * capture-safe.  YMS_ERR_INVALID: nviews outside 1..8, a NULL pointer, an empty range or one outside
+ * [0, A[v]], a flip outside 0..3, a size < 1, n outside 1..65535, nc < 1, a view with A[v] * (4+nc) >= 2^31, or R * nc >= 2^31.  Any
+ * nc >= 1 (rows of 4+nc floats need only 4-byte alignment; 16-byte loads are used when 4+nc is a
+ * multiple of 4 and every base is 16-byte aligned).  out must not overlap an input.
+ *
+ * yms_det_finalize_vote: yms_det_finalize's contract with the same selection, scores, labels,
+ * anchors, counts, fill rows, frames un-map and clip; only the box of each emitted row i differs,
+ * taken before the un-map:
+ *   M_i   = { live rows j < cand_count[b] : nms_label[j] == nms_label[i] and (double)ovr(i, j) > iou }
+ *   box_i = sum_{j in M_i} score_j box_j / sum_{j in M_i} score_j   (float64 sums, one rounding to fp32)
+ * ovr is yms_nms_classwise's own fp32 expression (inter / (area_i + area_j - inter), areas (x2-x1)*(y2-y1),
+ * inter = max(0, xx2-xx1) * max(0, yy2-yy1)), evaluated by the same device function.  nms_label [n][K]
+ * is the label array that was handed to yms_nms_classwise (all zero on live rows for class-agnostic
+ * NMS), cand_count[n] yms_det_candidates' count.  A row whose score sum is 0 or not finite keeps
+ * its own box: that covers an empty M_i (a zero-area box: its ovr with itself is NaN; iou >= 1) and
+ * a +inf score.  A NaN overlap never makes a member.  The float64 summation order is fixed, so the
+ * output is deterministic; it is specified to one fp32 ulp of the exactly rounded mean, not bit for
+ * bit.  Ties in the selection as yms_det_finalize.  Two launches (det's box slots carry the row ids
+ * from the first to the second), no host read, no allocation: capture-safe.  YMS_ERR_INVALID as
+ * yms_det_finalize, and for a NULL cand_count / nms_label, a NaN iou or n > 65535. */
+#define YMS_TTA_MAX_VIEWS 8
+yms_status yms_tta_merge(int n, int nc, int nviews, const float* const* preds, const int* A, const int* a0,
+                         const int* a1, const int* H, const int* W, const int* flips,
+                         const float* const* frames, float* out, void* stream);
+yms_status yms_det_finalize_vote(int n, int K, int max_det, const float* cand_boxes, const float* cand_score,
+                                 const int* true_label, const int* cand_anchor, const int64_t* keep_idx,
+                                 const int* counts, const float* frames, const int* cand_count,
+                                 const int* nms_label, double iou, float* det, int* det_anchor, int* det_count,
+                                 void* stream);
 
 /* ---- optimizer step: SGD / Adam + weight EMA + norm clipping + non-finite skip ------------ */
 /* Replaces torch.optim.SGD / Adam behind tools/utils.py:11-25 get_optimizer, the

@@ -26,6 +26,13 @@
 // Finalize.  One workgroup per image: the kept rows' unique 48-bit keys (score bits, then lower row
 // first) go through a radix select when there are more than max_det, the survivors (<= 1024) are
 // sorted in LDS, and the boxes are un-letterboxed with separately rounded fp32 operations.
+//
+// Box voting (yms_det_finalize_vote).  The same ranking, instantiated to leave each emitted
+// detection's candidate row id in its box slot; a second launch then runs one wavefront per emitted
+// detection over the image's live candidate rows, sums score * box and score in float64 over the rows
+// of its NMS label that the NMS's own predicate (iou_gt, nms_pick.hpp) puts above the threshold, and
+// overwrites the slot with the mean, un-letterboxed as above.  n * max_det wavefronts of at most K
+// pair tests each, whatever the NMS kept.
 #include "nms_pick.hpp"
 
 #pragma clang fp contract(off)
@@ -332,6 +339,8 @@ __global__ __launch_bounds__(256) void det_write_kernel(DetArgs d, int K, DetWs 
 // ---------------------------------------------------------------------------------------
 // finalize
 // ---------------------------------------------------------------------------------------
+// VOTE: the box slot of an emitted row carries its candidate row id (int bits in o[0]) to det_vote_kernel.
+template <bool VOTE>
 __global__ __launch_bounds__(1024) void det_finalize_kernel(int K, int max_det, const float4* cand_boxes,
                                                             const float* cand_score, const int* true_label,
                                                             const int* cand_anchor, const int64_t* keep_idx,
@@ -415,8 +424,8 @@ __global__ __launch_bounds__(1024) void det_finalize_kernel(int K, int max_det, 
     float* o = det + ((size_t)b * max_det + tid) * 6;
     if (tid < m) {
       const int r = 0x1ffff - (int)(s_key[tid] & 0x1ffffu);
-      float4 q = cand_boxes[(size_t)b * K + r];
-      if (frames) {
+      float4 q = VOTE ? make_float4(0.f, 0.f, 0.f, 0.f) : cand_boxes[(size_t)b * K + r];
+      if (!VOTE && frames) {
         const float* f = frames + 6 * (size_t)b;  // gain_x, gain_y, pad_x, pad_y, w0, h0
         q.x = fminf(fmaxf((q.x - f[2]) / f[0], 0.f), f[4]);
         q.y = fminf(fmaxf((q.y - f[3]) / f[1], 0.f), f[5]);
@@ -424,6 +433,7 @@ __global__ __launch_bounds__(1024) void det_finalize_kernel(int K, int max_det, 
         q.w = fminf(fmaxf((q.w - f[3]) / f[1], 0.f), f[5]);
       }
       o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+      if (VOTE) reinterpret_cast<int*>(o)[0] = r;
       o[4] = sc[r];
       o[5] = (float)true_label[(size_t)b * K + r];
       det_anchor[(size_t)b * max_det + tid] = cand_anchor[(size_t)b * K + r];
@@ -433,6 +443,60 @@ __global__ __launch_bounds__(1024) void det_finalize_kernel(int K, int max_det, 
       det_anchor[(size_t)b * max_det + tid] = -1;
     }
   }
+}
+
+// One wavefront per emitted detection (b, i), 4 per block: grid (ceil(max_det / 4), n).  Row r of the
+// detection comes from det_finalize_kernel<true>; the members are the live rows j < cand_count[b] with
+// r's NMS label and iou_gt(r, j).  Sums in float64 (lane-strided, then a xor-shuffle tree: a fixed
+// order), one rounding to fp32.  A score sum that is 0 (no member: a zero-area box's overlap with
+// itself is NaN) or not finite (+inf score) leaves the row its own box.
+__global__ __launch_bounds__(256) void det_vote_kernel(int K, int max_det, const float4* cand_boxes,
+                                                       const float* cand_score, const int* nms_label,
+                                                       const int* cand_count, double iou, const float* frames,
+                                                       float* det, const int* det_count) {
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);          // uniform for the wavefront
+  if (i >= max_det || i >= det_count[b]) return;
+  float* o = det + ((size_t)b * max_det + i) * 6;
+  const int r = reinterpret_cast<const int*>(o)[0];
+  if (r < 0 || r >= K) return;
+  const int cnt = min(max(cand_count[b], 0), K);
+  const float4* bx = cand_boxes + (size_t)b * K;
+  const float* sc = cand_score + (size_t)b * K;
+  const int* lb = nms_label + (size_t)b * K;
+  const float4 bi = bx[r];
+  const int li = lb[r];
+  double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (int j = lane; j < cnt; j += 64) {
+    if (lb[j] != li) continue;
+    const float4 bj = bx[j];
+    if (!iou_gt(bi, bj, iou)) continue;
+    const double w = (double)sc[j];
+    sw += w;
+    s0 += w * (double)bj.x;
+    s1 += w * (double)bj.y;
+    s2 += w * (double)bj.z;
+    s3 += w * (double)bj.w;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sw += __shfl_xor(sw, off);
+    s0 += __shfl_xor(s0, off);
+    s1 += __shfl_xor(s1, off);
+    s2 += __shfl_xor(s2, off);
+    s3 += __shfl_xor(s3, off);
+  }
+  if (lane != 0) return;
+  float4 q = bi;
+  if (sw != 0.0 && isfinite(sw)) q = make_float4((float)(s0 / sw), (float)(s1 / sw), (float)(s2 / sw), (float)(s3 / sw));
+  if (frames) {
+    const float* f = frames + 6 * (size_t)b;
+    q.x = fminf(fmaxf((q.x - f[2]) / f[0], 0.f), f[4]);
+    q.y = fminf(fmaxf((q.y - f[3]) / f[1], 0.f), f[5]);
+    q.z = fminf(fmaxf((q.z - f[2]) / f[0], 0.f), f[4]);
+    q.w = fminf(fmaxf((q.w - f[3]) / f[1], 0.f), f[5]);
+  }
+  o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
 }
 
 }  // namespace yms
@@ -505,9 +569,28 @@ yms_status yms_det_finalize(int n, int K, int max_det, const float* cand_boxes, 
       !det_count)
     return YMS_ERR_INVALID;
   if ((uintptr_t)cand_boxes % 16 != 0) return YMS_ERR_INVALID;
-  hipLaunchKernelGGL(det_finalize_kernel, dim3((unsigned)n), dim3(1024), 0, (hipStream_t)stream, K, max_det,
+  hipLaunchKernelGGL(det_finalize_kernel<false>, dim3((unsigned)n), dim3(1024), 0, (hipStream_t)stream, K, max_det,
                      reinterpret_cast<const float4*>(cand_boxes), cand_score, true_label, cand_anchor, keep_idx,
                      counts, frames, det, det_anchor, det_count);
+  return launch_status();
+}
+
+yms_status yms_det_finalize_vote(int n, int K, int max_det, const float* cand_boxes, const float* cand_score,
+                                 const int* true_label, const int* cand_anchor, const int64_t* keep_idx,
+                                 const int* counts, const float* frames, const int* cand_count,
+                                 const int* nms_label, double iou, float* det, int* det_anchor, int* det_count,
+                                 void* stream) {
+  if (n <= 0 || n > 65535 || K < 1 || K > DET_MAX_K || max_det < 1 || max_det > DET_MAX_DET) return YMS_ERR_INVALID;
+  if (!cand_boxes || !cand_score || !true_label || !cand_anchor || !keep_idx || !counts || !cand_count ||
+      !nms_label || !det || !det_anchor || !det_count)
+    return YMS_ERR_INVALID;
+  if ((uintptr_t)cand_boxes % 16 != 0 || iou != iou) return YMS_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const float4* cb = reinterpret_cast<const float4*>(cand_boxes);
+  hipLaunchKernelGGL(det_finalize_kernel<true>, dim3((unsigned)n), dim3(1024), 0, st, K, max_det, cb, cand_score,
+                     true_label, cand_anchor, keep_idx, counts, frames, det, det_anchor, det_count);
+  hipLaunchKernelGGL(det_vote_kernel, dim3((unsigned)cdiv(max_det, 4), (unsigned)n), dim3(256), 0, st, K, max_det,
+                     cb, cand_score, nms_label, cand_count, iou, frames, det, det_count);
   return launch_status();
 }
 

@@ -150,19 +150,7 @@ __device__ __forceinline__ uint32_t orderable(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__device__ __forceinline__ bool iou_gt(const float4& i, const float4& j, double thr) {
-  const float iarea = (i.z - i.x) * (i.w - i.y);
-  const float jarea = (j.z - j.x) * (j.w - j.y);
-  const float xx1 = fmaxf(i.x, j.x);
-  const float yy1 = fmaxf(i.y, j.y);
-  const float xx2 = fminf(i.z, j.z);
-  const float yy2 = fminf(i.w, j.w);
-  const float w = fmaxf(0.0f, xx2 - xx1);
-  const float h = fmaxf(0.0f, yy2 - yy1);
-  const float inter = w * h;
-  const float ovr = inter / (iarea + jarea - inter);
-  return (double)ovr > thr;
-}
+// iou_gt: nms_pick.hpp (shared with detect.hip's box voting)
 
 // Graph NMS (segments of gmin..NMS_GR_MAXN finite boxes, threshold >= 0; see nms_graph_*).
 constexpr int NMS_GR_MAXN = 8192;

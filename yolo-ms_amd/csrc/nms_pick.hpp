@@ -1,5 +1,6 @@
 // What the NMS prep decides per anchor, shared by nms_prep_kernel (head_nms.hip) and the candidate
-// stage of the COCO-protocol detect (detect.hip), so both write the same bits for the same anchor.
+// stage of the COCO-protocol detect (detect.hip), so both write the same bits for the same anchor;
+// and the NMS's overlap predicate, shared by its kernels and detect.hip's box voting.
 #pragma once
 #include "yms_common.hpp"
 
@@ -40,6 +41,23 @@ __device__ __forceinline__ void nms_pick16(const float* q, int nc, int sub, floa
 __device__ __forceinline__ float4 nms_xyxy(const float* q) {
   const float cx = q[0], cy = q[1], w = q[2], h = q[3];
   return make_float4(cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2);
+}
+
+// The NMS's overlap predicate, torchvision's CPU kernel op for op (fp32, no +1, the ratio compared as
+// a double); the class-wise NMS kernels and the box voting of yms_det_finalize_vote decide with this
+// one function, so that no rounding can make the two disagree on a pair.
+__device__ __forceinline__ bool iou_gt(const float4& i, const float4& j, double thr) {
+  const float iarea = (i.z - i.x) * (i.w - i.y);
+  const float jarea = (j.z - j.x) * (j.w - j.y);
+  const float xx1 = fmaxf(i.x, j.x);
+  const float yy1 = fmaxf(i.y, j.y);
+  const float xx2 = fminf(i.z, j.z);
+  const float yy2 = fminf(i.w, j.w);
+  const float w = fmaxf(0.0f, xx2 - xx1);
+  const float h = fmaxf(0.0f, yy2 - yy1);
+  const float inter = w * h;
+  const float ovr = inter / (iarea + jarea - inter);
+  return (double)ovr > thr;
 }
 
 }  // namespace yms

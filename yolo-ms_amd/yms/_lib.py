@@ -230,6 +230,8 @@ _SIGS = {
     "yms_det_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "yms_det_candidates": (_I, [_I, _I, _I, _P, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "yms_det_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "yms_det_finalize_vote": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P]),
+    "yms_tta_merge": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "yms_optim_chunk_elems": (_I, []),
     "yms_optim_table_chunks": (_L, [_I, _P]),
     "yms_optim_table_bytes": (_SZ, [_I, _P]),

@@ -162,7 +162,7 @@ def _class_mask(dev, nc, classes):
 
 
 def detect(pred, conf=0.25, iou=0.45, *, multi_label=False, agnostic=False, classes=None, max_det=300,
-           max_nms=30000, frames=None):
+           max_nms=30000, frames=None, vote=False):
     """The post-process of the published YOLOv8 / YOLO-MS AP protocol on decoded predictions
     [B, A, 4+nc] (fp32; (cx, cy, w, h) in input pixels + class scores) -> :class:`Detections`.
 
@@ -174,7 +174,11 @@ def detect(pred, conf=0.25, iou=0.45, *, multi_label=False, agnostic=False, clas
     candidate row ascending, rows being in ascending anchor * nc + class order).  ``frames``: a
     [B, 6] device tensor (gain_x, gain_y, pad_x, pad_y, w0, h0) -- or yms.data's Frames -- maps the
     boxes back to each original image, min(max((v - pad) / gain, 0), w0 | h0); boxes wholly in the
-    padding stay, with zero area.  These tie rules are this package's; ultralytics leaves ties to
+    padding stay, with zero area.  ``vote`` (ultralytics' merge=True, the companion of yms.tta's view
+    merge): each detection's box becomes, before that un-map, the score-weighted mean of the candidate
+    rows of its NMS class (agnostic: of all) whose IoU with it -- the NMS's own fp32 expression --
+    exceeds ``iou``, summed in float64 and rounded once; a detection whose weights sum to 0 or to a
+    non-finite number keeps its box.  Scores, labels, anchors and the selection do not change.  These tie rules are this package's; ultralytics leaves ties to
     its sort (parity UNPINNED).  No host synchronisation; ``Detections.to_list()`` is the one sync."""
     _cuda(pred)
     if pred.dim() != 3 or pred.shape[2] < 5 or pred.shape[0] < 1 or pred.shape[1] < 1:
@@ -230,7 +234,12 @@ def detect(pred, conf=0.25, iou=0.45, *, multi_label=False, agnostic=False, clas
     det = torch.empty((B, max_det, 6), dtype=torch.float32, device=dev)
     danchor = torch.empty((B, max_det), **i32)
     dcount = torch.empty(B, **i32)
-    L.call("yms_det_finalize", B, K, max_det, cbox.data_ptr(), cscore.data_ptr(), clabel.data_ptr(),
-           canchor.data_ptr(), keep.data_ptr(), kcount.data_ptr(), L.ptr(frames), det.data_ptr(),
-           danchor.data_ptr(), dcount.data_ptr(), st)
+    if vote:
+        L.call("yms_det_finalize_vote", B, K, max_det, cbox.data_ptr(), cscore.data_ptr(), clabel.data_ptr(),
+               canchor.data_ptr(), keep.data_ptr(), kcount.data_ptr(), L.ptr(frames), ccount.data_ptr(),
+               nlabel.data_ptr(), ctypes.c_double(iou), det.data_ptr(), danchor.data_ptr(), dcount.data_ptr(), st)
+    else:
+        L.call("yms_det_finalize", B, K, max_det, cbox.data_ptr(), cscore.data_ptr(), clabel.data_ptr(),
+               canchor.data_ptr(), keep.data_ptr(), kcount.data_ptr(), L.ptr(frames), det.data_ptr(),
+               danchor.data_ptr(), dcount.data_ptr(), st)
     return Detections(det[..., :4], det[..., 4], det[..., 5].to(torch.int32), danchor, dcount, ctotal)
