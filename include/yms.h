@@ -395,9 +395,11 @@ yms_status yms_map_accumulate(int n_det, const float* scores, const int* labels,
 /* ---- COCO AP: mAP@[.5:.95], AP by object size, AR@1/10/100 (torchmetrics' default construction) ---- */
 /* GPU: the matching of yms_map_match for n_thr (1..16) increasing IoU thresholds in (0, 1]
  * (iou_thrs: HOST array) times COCOeval's four area ranges all / small / medium / large
- * ([0,1e10], [0,32^2], [32^2,96^2], [96^2,1e10], both ends inclusive, area = w*h), bbox, no crowd:
- * out-of-range ground truths are ignore (visited after the in-range ones, taken only when no in-range
- * one qualifies); a detection matched to one, or unmatched and itself out of range, is ignored.
+ * ([0,1e10], [0,32^2], [32^2,96^2], [96^2,1e10], both ends inclusive), on boxes.  This entry point takes
+ * every ground truth as an ordinary one whose area is w*h; yms_map_match_coco_gt below adds COCOeval's
+ * iscrowd and annotation area.  Out-of-range ground truths are ignore (visited after the in-range ones,
+ * taken only when no in-range one qualifies); a detection matched to one, or unmatched and itself out of
+ * range, is ignored.
  *   matched[a * n_det + d], ignored[a * n_det + d]: bit t = at threshold t (area range a)
  *   gt_ignore[g]: bit a = ground truth g is out of area range a
  *   rank_ws: 2 * n_det ints; the first n_det receive the per-class rank (kept = rank < 100)
@@ -407,6 +409,23 @@ yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, c
                               const int* gt_off, int n_thr, const double* iou_thrs, uint16_t* matched,
                               uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws, int max_gt_per_image,
                               void* stream);
+/* GPU: yms_map_match_coco with COCOeval's two per-annotation fields (evaluateImg / computeIoU), indexed
+ * like gt_labels, each NULL or given on its own; with both NULL every output byte is yms_map_match_coco's.
+ *   gt_area[g] (float, compared as double): the annotation's area -- on COCO the mask's -- decides the
+ *     ground truth's area ranges instead of w*h.  The comparisons are the same: a negative area is out of
+ *     every range, a NaN inside every one.  A detection's own area stays w*h.
+ *   gt_crowd[g] != 0: a crowd (iscrowd) ground truth.  It is ignore in all four ranges and keeps its input
+ *     position among its class' ignored ground truths; its IoU with a detection is intersection /
+ *     detection area; it is never used up, so any number of detections can match it; a detection whose
+ *     best candidate is a crowd is matched and ignored (neither TP nor FP).  An in-range match still wins
+ *     over any ignored one, and among equal IoUs the later ground truth.
+ *   gt_ignore[g] reports a crowd as out of all four ranges (low bits 1111), so counting the zero bits
+ *     gives the non-ignored ground truths unchanged. */
+yms_status yms_map_match_coco_gt(int n_images, int n_det, const float* det_boxes, const float* det_scores,
+                                 const int* det_labels, const int* det_off, const float* gt_boxes,
+                                 const int* gt_labels, const int* gt_off, int n_thr, const double* iou_thrs,
+                                 uint16_t* matched, uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws,
+                                 int max_gt_per_image, const uint8_t* gt_crowd, const float* gt_area, void* stream);
 /* HOST (not stream-ordered; host arrays in evaluation order): COCOeval.accumulate for maxDets
  * 1 / 10 / 100 -> precision[n_thr][101][n_classes][4][3] and recall[n_thr][n_classes][4][3], -1 where
  * npig[class * 4 + area] (the number of non-ignored ground truths) is 0. */
@@ -432,6 +451,15 @@ yms_status yms_map_match_coco_fixed(int n_images, int max_det, const float* det_
                                     const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
                                     int n_classes, long cap, long row0, float* score, int* label, int* rank,
                                     uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws, void* stream);
+/* GPU: the padded-layout matching with yms_map_match_coco_gt's gt_crowd / gt_area, laid out
+ * [n_images][max_gt] like gt_labels, each NULL or given on its own (both NULL: yms_map_match_coco_fixed).
+ * npig leaves every crowd ground truth out and sorts the others by gt_area where it is given. */
+yms_status yms_map_match_coco_fixed_gt(int n_images, int max_det, const float* det_boxes, const float* det_scores,
+                                       const int* det_labels, const int* det_count, int max_gt, const float* gt_boxes,
+                                       const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
+                                       int n_classes, long cap, long row0, float* score, int* label, int* rank,
+                                       uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws,
+                                       const uint8_t* gt_crowd, const float* gt_area, void* stream);
 /* GPU: yms_map_accumulate_coco over the first n_rows rows of those epoch buffers (cap: the masks'
  * area stride; image = row / max_det, so row order is the host's (image, index) order) -> DEVICE
  * precision[n_thr][101][n_classes][4][3] and recall[n_thr][n_classes][4][3], float64, bit-identical

@@ -11,7 +11,13 @@ Each repetition times one whole epoch (reset, every update, compute) between dev
 wall clock (the clock stops after compute(), which ends in a host read); the two alternate, after one
 untimed warm-up epoch each.  Prints the times per repetition, their spread, and whether the two
 evaluators' tables and summaries agree on this workload.
-Usage: python tools/map_dev_micro.py [--images 5000] [--reps 3] [--batch 32]"""
+--crowd F (default 0: the workload above, untouched) marks a fraction F of the ground truths crowd and gives
+every one an annotation area u * w*h, u ~ U(0.3, 1), drawn from a generator of their own; both evaluators
+then take them (iscrowd / area keys, gt_crowd / gt_area), i.e. the matching runs its crowd-aware kernels.
+After those repetitions the device evaluator is timed --reps more times in two parts with a synchronise between
+them: reset + every update (the match kernel), and compute() (device accumulate, summary, host read).
+--tree DIR imports yms from another checkout's DIR/yolo-ms_amd (an A/B run of this script against another build).
+Usage: python tools/map_dev_micro.py [--images 5000] [--reps 3] [--batch 32] [--crowd 0.15] [--tree DIR]"""
 import argparse
 import os
 import sys
@@ -61,18 +67,33 @@ def main():
     ap.add_argument("--images", type=int, default=5000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--crowd", type=float, default=0.0)
+    ap.add_argument("--tree", default=None)
     a = ap.parse_args()
+    if a.tree:
+        sys.path[:0] = [os.path.abspath(a.tree), os.path.join(os.path.abspath(a.tree), "yolo-ms_amd")]
     if not torch.cuda.is_available():
         sys.exit("map_dev_micro: needs a ROCm GPU (no CPU fallback)")
     from yms.metrics import CocoEvaluator, MeanAveragePrecision
+    import yms.metrics
+    print(f"# yms build {'with' if hasattr(yms.metrics, 'coco_results') else 'without'} iscrowd / area support"
+          f"{' (--tree)' if a.tree else ''}", flush=True)
     N, B = a.images, a.batch
     boxes, scores, labels, targets = epoch(N)
+    if a.crowd > 0:
+        rng = np.random.default_rng(1)
+        for t in targets:
+            k, b = len(t["labels"]), t["boxes"]
+            t["iscrowd"] = (rng.random(k) < a.crowd).astype(np.uint8)
+            t["area"] = (rng.uniform(0.3, 1.0, k) * (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])).astype(np.float32)
     db, ds, dl = (torch.from_numpy(x).cuda() for x in (boxes, scores, labels))
     counts = torch.full((N,), MAX_DET, dtype=torch.int32, device="cuda")
     dev_batches, list_batches = [], []
     for i in range(0, N, B):
         j = min(i + B, N)
-        dev_batches.append(((db[i:j], ds[i:j], dl[i:j], counts[i:j]), CocoEvaluator.pad_targets(targets[i:j], "cuda")))
+        gts = CocoEvaluator.pad_targets(targets[i:j], "cuda", flags=True) if a.crowd > 0 \
+            else CocoEvaluator.pad_targets(targets[i:j], "cuda")
+        dev_batches.append(((db[i:j], ds[i:j], dl[i:j], counts[i:j]), gts))
         list_batches.append(([{"boxes": db[k], "scores": ds[k], "labels": dl[k]} for k in range(i, j)],
                              [{k2: torch.from_numpy(v).cuda() for k2, v in t.items()} for t in targets[i:j]]))
     ev, metric = CocoEvaluator(NC, capacity_images=max(1024, N)), MeanAveragePrecision()
@@ -100,6 +121,8 @@ def main():
         return out, s.elapsed_time(e), (time.perf_counter() - t0) * 1e3
 
     n_gt = sum(len(t["labels"]) for t in targets)
+    if a.crowd > 0:
+        print(f"# crowd path: {sum(int(t['iscrowd'].sum()) for t in targets)} crowd ground truths, area = u * w*h", flush=True)
     print(f"# {N} images x {MAX_DET} detections = {N * MAX_DET} rows, {NC} classes, {n_gt} ground truths "
           f"({n_gt / N:.2f} per image), {len(dev_batches)} updates of {B}; one warm-up epoch each, then {a.reps} "
           f"alternating repetitions of reset + updates + compute", flush=True)
@@ -118,6 +141,21 @@ def main():
     for label, v in t.items():
         print(f"# {label:6s} wall: median {np.median(v):.2f} ms, spread (max - min) {max(v) - min(v):.2f} ms")
     print(f"# list / device (median wall): {np.median(t['list']) / np.median(t['device']):.1f}x")
+
+    def updates():
+        ev.reset()
+        for dets, gts in dev_batches:
+            ev.update(dets, *gts)
+
+    parts = {"updates": [], "compute": []}
+    for r in range(a.reps):
+        for label, fn in (("updates", updates), ("compute", ev.compute)):
+            _, ev_ms, wall_ms = timed(fn)
+            parts[label].append(wall_ms)
+        print(f"rep {r} device in parts: updates {parts['updates'][-1]:8.2f} ms  compute {parts['compute'][-1]:8.2f} ms "
+              f"(wall)", flush=True)
+    for label, v in parts.items():
+        print(f"# device {label:7s} wall: median {np.median(v):.2f} ms, min {min(v):.2f} max {max(v):.2f}")
 
 
 if __name__ == "__main__":

@@ -13,7 +13,10 @@
 // for up to 16 IoU thresholds x the four COCOeval area ranges at once, one (threshold, area) pair per
 // lane, with COCOeval's ignore rules (out-of-range ground truths are visited last and only taken when
 // no in-range one qualifies; a detection matched to one, or unmatched and itself out of range, is
-// ignored); yms_map_accumulate_coco fills COCOeval's precision / recall tables on the host.
+// ignored); yms_map_accumulate_coco fills COCOeval's precision / recall tables on the host.  The _gt entry
+// points add COCOeval's two per-annotation fields: iscrowd (a crowd ground truth is ignore in every range,
+// scored as intersection / detection area, and may be matched by any number of detections) and area (the
+// annotation's own area decides its size class instead of w*h).
 // map_match_coco_fixed_kernel is the same matching on yms.ops.detect's padded layout, written into the
 // epoch buffers that csrc/map_accum.hip accumulates on the device.
 #include <algorithm>
@@ -141,16 +144,20 @@ __device__ __forceinline__ unsigned map_area_out_bits(double area) {
   return b;
 }
 
-// maskUtils.iou on xywh doubles, every product and sum rounded on its own as numpy does
+// gig[] bit 4: the ground truth is a crowd (bits 0..3: out of area range a)
+constexpr unsigned MAP_GT_CROWD = 16u;
+
+// maskUtils.iou on xywh doubles, every product and sum rounded on its own as numpy does; against a crowd
+// ground truth the union is the detection's own area (intersection over detection area)
 __device__ __forceinline__ double map_iou_xywh(double bx, double by, double bw, double bh, double gx, double gy,
-                                               double gw, double gh) {
+                                               double gw, double gh, bool crowd) {
 #pragma clang fp contract(off)
   const double w = fmin(bx + bw, gx + gw) - fmax(bx, gx);
   const double h = fmin(by + bh, gy + gh) - fmax(by, gy);
   if (!(w > 0.0 && h > 0.0)) return 0.0;
   const double inter = w * h;
   const double a = bw * bh, b = gw * gh;
-  return inter / (a + b - inter);
+  return inter / (crowd ? a : a + b - inter);
 }
 
 // One workgroup (4 waves) per image.  Setup: the image's ground truths are staged in LDS as xywh
@@ -163,10 +170,24 @@ __device__ __forceinline__ double map_iou_xywh(double bx, double by, double bw, 
 // (later one on ties) and takes the in-range one if there is any (COCOeval's break).  The "already
 // matched" bits are one LDS word column per lane (gm[wave][word][lane]): no lane shares a word, and
 // classes own disjoint bits, so they are cleared once.  There is no barrier after the setup.
+// GT = the per-ground-truth fields of COCOeval's evaluateImg / computeIoU are given (gt_crowd, gt_area: each
+// may still be null on its own; with GT = false neither is read and the code is the one without them):
+//   area ranges: a ground truth's range bits come from (double)gt_area[j] when given, else from w*h; the
+//     comparisons are map_area_out_bits' (a negative area is out of every range, a NaN inside every one);
+//   crowd as ignore: gt_crowd[j] != 0 makes the ground truth ignore in all four ranges.  It stays at its
+//     (class, input index) place, so crowd and out-of-range ground truths interleave by input index as in
+//     COCOeval's stable sort on the ignore flag, and the "later one on ties" rule covers both;
+//   crowd IoU: intersection / detection area (map_iou_xywh's crowd form);
+//   repeated matching: the "already matched" test is skipped for a crowd, so any number of detections can
+//     take the same one; a detection whose best candidate is a crowd is matched and ignored; an in-range
+//     match still wins over any ignored one.
+// The crowd flag is bit 4 of gig[]; gt_area is only read during the setup.
 // The body is shared by the two layouts (prefix offsets / padded rows): every pointer is the image's
 // own first detection / ground truth, nd / ng its counts, mstride the masks' area stride.
+template <bool GT>
 __device__ __forceinline__ void map_match_coco_image(const float* dbox, const float* dscore, const int* dlabel,
-                                                     int nd, const float* gbox, const int* glabel, int ng,
+                                                     int nd, const float* gbox, const int* glabel,
+                                                     const uint8_t* gt_crowd, const float* gt_area, int ng,
                                                      const MapCocoThr& P, long mstride, uint16_t* dmatch,
                                                      uint16_t* dign, uint8_t* gign_out, int* rank_out,
                                                      int* order_ws) {
@@ -176,6 +197,8 @@ __device__ __forceinline__ void map_match_coco_image(const float* dbox, const fl
   __shared__ uint8_t gig[MAP_MAX_GT];
   __shared__ unsigned gm[MAP_COCO_WAVES][MAP_MAX_GT / 32][64];
   __shared__ int n_heads;
+  static_assert(sizeof(gb) + sizeof(gl) + sizeof(heads) + sizeof(gig) + sizeof(gm) + sizeof(int) <= 160 * 1024,
+                "the matching's LDS arrays must fit one workgroup's 160 KB");
   constexpr int NT = 64 * MAP_COCO_WAVES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (ng > MAP_MAX_GT) return;            // the host entry point refuses these; never index past the LDS arrays
@@ -197,9 +220,10 @@ __device__ __forceinline__ void map_match_coco_image(const float* dbox, const fl
     gb[p][2] = gw;
     gb[p][3] = gh;
     gl[p] = lab;
-    const unsigned bits = map_area_out_bits(gw * gh);
+    unsigned bits = map_area_out_bits(GT && gt_area ? (double)gt_area[j] : gw * gh);
+    if (GT && gt_crowd && gt_crowd[j]) bits = MAP_GT_CROWD | 15u;
     gig[p] = (uint8_t)bits;
-    if (gign_out) gign_out[j] = (uint8_t)bits;
+    if (gign_out) gign_out[j] = (uint8_t)(bits & 15u);
   }
   for (int w = 0; w < (ng + 31) / 32; ++w) gm[wave][w][lane] = 0u;
   // detections: rank within the class (stable descending score), position in (class, rank) order,
@@ -262,14 +286,16 @@ __device__ __forceinline__ void map_match_coco_image(const float* dbox, const fl
       for (int base = 0; base < gn; base += 64) {
         const int p = gs + base + lane;
         double iou = 0.0;
-        if (base + lane < gn) iou = map_iou_xywh(bx, by, bw, bh, gb[p][0], gb[p][1], gb[p][2], gb[p][3]);
+        if (base + lane < gn)
+          iou = map_iou_xywh(bx, by, bw, bh, gb[p][0], gb[p][1], gb[p][2], gb[p][3], GT && (gig[p] & MAP_GT_CROWD));
         unsigned long long cand = __ballot(base + lane < gn && iou >= thr_min);
         while (cand) {                                 // wave-uniform: candidates in visiting order
           const int src = __ffsll((long long)cand) - 1;
           cand &= cand - 1;
           const double ci = __shfl(iou, src);
           const int cp = gs + base + src;
-          if (!live || ((gm[wave][cp >> 5][lane] >> (cp & 31)) & 1u)) continue;
+          const bool crowd = GT && (gig[cp] & MAP_GT_CROWD);      // cp is uniform: a crowd is never used up
+          if (!live || (!crowd && ((gm[wave][cp >> 5][lane] >> (cp & 31)) & 1u))) continue;
           if ((gig[cp] >> a) & 1u) {
             if (ci >= best_i) { best_i = ci; ji = cp; }
           } else {
@@ -290,26 +316,31 @@ __device__ __forceinline__ void map_match_coco_image(const float* dbox, const fl
   }
 }
 
+template <bool GT>
 __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_kernel(
     const float* dbox, const float* dscore, const int* dlabel, const int* doff, const float* gbox, const int* glabel,
-    const int* goff, MapCocoThr P, long n_det, uint16_t* dmatch, uint16_t* dign, uint8_t* gign_out, int* rank_out,
-    int* order_ws) {
+    const uint8_t* gt_crowd, const float* gt_area, const int* goff, MapCocoThr P, long n_det, uint16_t* dmatch,
+    uint16_t* dign, uint8_t* gign_out, int* rank_out, int* order_ws) {
   const int img = blockIdx.x;
   const int d0 = doff[img], nd = doff[img + 1] - d0;
   const int g0 = goff[img], ng = goff[img + 1] - g0;
-  map_match_coco_image(dbox + (long)d0 * 4, dscore + d0, dlabel + d0, nd, gbox + (long)g0 * 4, glabel + g0, ng, P,
-                       n_det, dmatch + d0, dign + d0, gign_out + g0, rank_out + d0, order_ws + d0);
+  map_match_coco_image<GT>(dbox + (long)d0 * 4, dscore + d0, dlabel + d0, nd, gbox + (long)g0 * 4, glabel + g0,
+                           GT && gt_crowd ? gt_crowd + g0 : nullptr, GT && gt_area ? gt_area + g0 : nullptr, ng, P,
+                           n_det, dmatch + d0, dign + d0, gign_out + g0, rank_out + d0, order_ws + d0);
 }
 
 // The padded layout of yms.ops.detect: image i owns rows [i * max_det, (i + 1) * max_det) of the inputs and
 // rows row0 + the same of the epoch buffers (masks: area stride cap).  Counts are read on the device and
 // clamped to the padded widths.  Every owned row is written: dead rows (slot >= count) get score 0, label -1,
 // rank -1 and zero masks; live rows the shared matching's results plus a copy of their score and label.
-// npig[class][area] += the image's ground truths that are in range (integer atomics).
+// npig[class][area] += the image's ground truths that are in range (integer atomics): never a crowd, and by
+// gt_area where it is given.
+template <bool GT>
 __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_fixed_kernel(
     const float* dbox, const float* dscore, const int* dlabel, const int* dcount, int max_det, const float* gbox,
-    const int* glabel, const int* gcount, int max_gt, MapCocoThr P, int n_classes, long cap, long row0, float* score,
-    int* label, int* rank_out, uint16_t* dmatch, uint16_t* dign, int* npig, int* order_ws) {
+    const int* glabel, const uint8_t* gt_crowd, const float* gt_area, const int* gcount, int max_gt, MapCocoThr P,
+    int n_classes, long cap, long row0, float* score, int* label, int* rank_out, uint16_t* dmatch, uint16_t* dign,
+    int* npig, int* order_ws) {
   constexpr int NT = 64 * MAP_COCO_WAVES;
   const int img = blockIdx.x, tid = threadIdx.x;
   const int nd = min(max(dcount[img], 0), max_det);
@@ -331,14 +362,17 @@ __global__ __launch_bounds__(64 * MAP_COCO_WAVES) void map_match_coco_fixed_kern
   for (int j = tid; j < ng; j += NT) {
     const int lab = glabel[gin0 + j];
     if (lab < 0 || lab >= n_classes) continue;
+    if (GT && gt_crowd && gt_crowd[gin0 + j]) continue;
     const float* q = gbox + (gin0 + j) * 4;
-    const unsigned bits = map_area_out_bits((double)(q[2] - q[0]) * (double)(q[3] - q[1]));
+    const unsigned bits = map_area_out_bits(GT && gt_area ? (double)gt_area[gin0 + j]
+                                                          : (double)(q[2] - q[0]) * (double)(q[3] - q[1]));
 #pragma unroll
     for (int a = 0; a < MAP_N_AREA; ++a)
       if (!((bits >> a) & 1u)) atomicAdd(&npig[lab * MAP_N_AREA + a], 1);
   }
-  map_match_coco_image(dbox + in0 * 4, dscore + in0, dlabel + in0, nd, gbox + gin0 * 4, glabel + gin0, ng, P, cap,
-                       dmatch + out0, dign + out0, nullptr, rank_out + out0, order_ws + in0);
+  map_match_coco_image<GT>(dbox + in0 * 4, dscore + in0, dlabel + in0, nd, gbox + gin0 * 4, glabel + gin0,
+                           GT && gt_crowd ? gt_crowd + gin0 : nullptr, GT && gt_area ? gt_area + gin0 : nullptr, ng,
+                           P, cap, dmatch + out0, dign + out0, nullptr, rank_out + out0, order_ws + in0);
 }
 
 }  // namespace yms
@@ -425,12 +459,13 @@ yms_status yms_map_accumulate(int n_det, const float* scores, const int* labels,
   return YMS_OK;
 }
 
-// T thresholds x 4 area ranges in one launch (COCOeval.evaluateImg, bbox, no crowd)
-yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, const float* det_scores,
-                              const int* det_labels, const int* det_off, const float* gt_boxes, const int* gt_labels,
-                              const int* gt_off, int n_thr, const double* iou_thrs, uint16_t* matched,
-                              uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws, int max_gt_per_image,
-                              void* stream) {
+// T thresholds x 4 area ranges in one launch (COCOeval.evaluateImg on boxes; gt_crowd / gt_area: the
+// annotations' iscrowd and area, each optional)
+yms_status yms_map_match_coco_gt(int n_images, int n_det, const float* det_boxes, const float* det_scores,
+                                 const int* det_labels, const int* det_off, const float* gt_boxes,
+                                 const int* gt_labels, const int* gt_off, int n_thr, const double* iou_thrs,
+                                 uint16_t* matched, uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws,
+                                 int max_gt_per_image, const uint8_t* gt_crowd, const float* gt_area, void* stream) {
   if (n_thr < 1 || n_thr > MAP_MAX_THR || !iou_thrs) return YMS_ERR_INVALID;
   MapCocoThr P;
   for (int t = 0; t < MAP_MAX_THR; ++t) P.thr[t] = t < n_thr ? iou_thrs[t] : 2.0;
@@ -443,18 +478,30 @@ yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, c
     return YMS_ERR_INVALID;
   if (max_gt_per_image < 0 || (max_gt_per_image > 0 && (!gt_boxes || !gt_labels || !gt_ignore))) return YMS_ERR_INVALID;
   if (max_gt_per_image > MAP_MAX_GT) return YMS_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(map_match_coco_kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0,
-                     (hipStream_t)stream, det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_off, P,
-                     (long)n_det, matched, ignored, gt_ignore, rank_ws, rank_ws + n_det);
+  auto kernel = (gt_crowd || gt_area) ? map_match_coco_kernel<true> : map_match_coco_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0, (hipStream_t)stream, det_boxes,
+                     det_scores, det_labels, det_off, gt_boxes, gt_labels, gt_crowd, gt_area, gt_off, P, (long)n_det,
+                     matched, ignored, gt_ignore, rank_ws, rank_ws + n_det);
   return launch_status();
 }
 
+yms_status yms_map_match_coco(int n_images, int n_det, const float* det_boxes, const float* det_scores,
+                              const int* det_labels, const int* det_off, const float* gt_boxes, const int* gt_labels,
+                              const int* gt_off, int n_thr, const double* iou_thrs, uint16_t* matched,
+                              uint16_t* ignored, uint8_t* gt_ignore, int* rank_ws, int max_gt_per_image,
+                              void* stream) {
+  return yms_map_match_coco_gt(n_images, n_det, det_boxes, det_scores, det_labels, det_off, gt_boxes, gt_labels,
+                               gt_off, n_thr, iou_thrs, matched, ignored, gt_ignore, rank_ws, max_gt_per_image,
+                               nullptr, nullptr, stream);
+}
+
 // the same matching on yms.ops.detect's padded layout, written into the epoch buffers of the device evaluator
-yms_status yms_map_match_coco_fixed(int n_images, int max_det, const float* det_boxes, const float* det_scores,
-                                    const int* det_labels, const int* det_count, int max_gt, const float* gt_boxes,
-                                    const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
-                                    int n_classes, long cap, long row0, float* score, int* label, int* rank,
-                                    uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws, void* stream) {
+yms_status yms_map_match_coco_fixed_gt(int n_images, int max_det, const float* det_boxes, const float* det_scores,
+                                       const int* det_labels, const int* det_count, int max_gt, const float* gt_boxes,
+                                       const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
+                                       int n_classes, long cap, long row0, float* score, int* label, int* rank,
+                                       uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws,
+                                       const uint8_t* gt_crowd, const float* gt_area, void* stream) {
   if (n_thr < 1 || n_thr > MAP_MAX_THR || !iou_thrs) return YMS_ERR_INVALID;
   MapCocoThr P;
   for (int t = 0; t < MAP_MAX_THR; ++t) P.thr[t] = t < n_thr ? iou_thrs[t] : 2.0;
@@ -470,10 +517,21 @@ yms_status yms_map_match_coco_fixed(int n_images, int max_det, const float* det_
       !ignored || !npig || !order_ws)
     return YMS_ERR_INVALID;
   if (max_gt > 0 && (!gt_boxes || !gt_labels)) return YMS_ERR_INVALID;
-  hipLaunchKernelGGL(map_match_coco_fixed_kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0,
-                     (hipStream_t)stream, det_boxes, det_scores, det_labels, det_count, max_det, gt_boxes, gt_labels,
-                     gt_count, max_gt, P, n_classes, cap, row0, score, label, rank, matched, ignored, npig, order_ws);
+  auto kernel = (gt_crowd || gt_area) ? map_match_coco_fixed_kernel<true> : map_match_coco_fixed_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_images), dim3(64 * MAP_COCO_WAVES), 0, (hipStream_t)stream, det_boxes,
+                     det_scores, det_labels, det_count, max_det, gt_boxes, gt_labels, gt_crowd, gt_area, gt_count,
+                     max_gt, P, n_classes, cap, row0, score, label, rank, matched, ignored, npig, order_ws);
   return launch_status();
+}
+
+yms_status yms_map_match_coco_fixed(int n_images, int max_det, const float* det_boxes, const float* det_scores,
+                                    const int* det_labels, const int* det_count, int max_gt, const float* gt_boxes,
+                                    const int* gt_labels, const int* gt_count, int n_thr, const double* iou_thrs,
+                                    int n_classes, long cap, long row0, float* score, int* label, int* rank,
+                                    uint16_t* matched, uint16_t* ignored, int* npig, int* order_ws, void* stream) {
+  return yms_map_match_coco_fixed_gt(n_images, max_det, det_boxes, det_scores, det_labels, det_count, max_gt,
+                                     gt_boxes, gt_labels, gt_count, n_thr, iou_thrs, n_classes, cap, row0, score,
+                                     label, rank, matched, ignored, npig, order_ws, nullptr, nullptr, stream);
 }
 
 // host: COCOeval.accumulate over T thresholds, 4 area ranges and maxDets 1 / 10 / 100

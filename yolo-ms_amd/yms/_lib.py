@@ -200,6 +200,9 @@ _SIGS = {
     "yms_map_accumulate_coco": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "yms_map_match_coco_fixed": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _L, _L, _P, _P, _P, _P, _P,
                                       _P, _P, _P]),
+    "yms_map_match_coco_gt": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "yms_map_match_coco_fixed_gt": (_I, [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _L, _L, _P, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P]),
     "yms_map_accumulate_coco_dev_ws_bytes": (_SZ, [_L, _I, _I]),
     "yms_map_accumulate_coco_dev": (_I, [_L, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "yms_det_loss_ws_bytes": (_SZ, [_I, _I, _I, _I]),

@@ -723,6 +723,26 @@ class COCODetection(torch.utils.data.Dataset):
             labels.append(lab)
         return boxes, labels
 
+    def eval_annotations(self, idx):
+        """The image's ground truths as COCOeval keeps them: every annotation of a known category, crowd
+        and zero-area ones included (``annotations`` drops those, as training must) -> {'boxes' [k, 4] fp32
+        xyxy in original-image pixels (where ``detect``'s letterbox un-mapping puts its detections), 'labels'
+        [k] int64, 'iscrowd' [k] uint8, 'area' [k] fp32: the annotation's own ``area`` -- the mask's on COCO
+        -- or w*h where it has none}, numpy arrays as ``CocoEvaluator.pad_targets(..., flags=True)`` and
+        ``MeanAveragePrecision.update`` take them."""
+        boxes, labels, crowd, area = [], [], [], []
+        for a in self.img_to_anns[self.image_ids[idx]]:
+            lab = self.cat2label.get(a["category_id"])
+            if lab is None:
+                continue
+            x, y, w, h = a["bbox"]
+            boxes.append([x, y, x + w, y + h])
+            labels.append(lab)
+            crowd.append(1 if a.get("iscrowd", 0) else 0)
+            area.append(a["area"] if "area" in a else w * h)
+        return {"boxes": np.asarray(boxes, np.float32).reshape(-1, 4), "labels": np.asarray(labels, np.int64),
+                "iscrowd": np.asarray(crowd, np.uint8), "area": np.asarray(area, np.float32)}
+
     def __getitem__(self, idx):
         from PIL import Image
         info = self.imgs[self.image_ids[idx]]
