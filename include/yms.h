@@ -28,6 +28,8 @@
  *                           yms_nms_classwise, opt-in
  *   yms_tta_merge,          nothing in the reference: test-time augmentation's view merge and box
  *   yms_det_finalize_vote   voting around the same detect, opt-in
+ *   yms_tile_merge          nothing in the reference: tiled (sliced) inference of large images, the
+ *                           gather of every tile's predictions in front of the same detect, opt-in
  *   yms_resize_normalize,   tools/dataset.py:84-134 transform list + collate_fn's stack (:260)
  *   yms_augment_normalize
  *   yms_mosaic_normalize    the config's `mosaic` / `mixup` keys, which dataset.py never reads:
@@ -696,6 +698,44 @@ yms_status yms_det_finalize_vote(int n, int K, int max_det, const float* cand_bo
                                  const int* counts, const float* frames, const int* cand_count,
                                  const int* nms_label, double iou, float* det, int* det_anchor, int* det_count,
                                  void* stream);
+
+/* ---- tiled inference of large images: the tiles' merge in front of yms_det_candidates ---------------- */
+/* Nothing in the reference.  Sliced inference (popularised by SAHI) cuts a large image into overlapping
+ * tiles at native resolution, runs every tile, maps each tile's predictions back and runs one NMS over
+ * all of them.  The grid and suppression rules are this package's (yms/tiles.py; parity with SAHI
+ * UNPINNED); this entry point is the gather.
+ *
+ * yms_tile_merge: pred [T, A, 4+nc] fp32, the decoded predictions (yms_head_decode's out; boxes (cx, cy,
+ * w, h) in tile-input pixels) of T tile inputs of one common size -> out [n, S * A, 4+nc] in
+ * original-image pixels.  table: DEVICE array of n * S yms_tile_slot records, record b * S + s being
+ * slot s of image b, which owns out's rows [s * A, (s + 1) * A) of image b, row s * A + a from row a of
+ * pred[tile].  S is the largest slot count of any image; an image with fewer leaves slots empty.
+ *   live slot (0 <= tile < T), per row, each operation separately rounded in fp32 (no contraction):
+ *     cx0 = (cx - pad_x) / gain_x;  cy0 = (cy - pad_y) / gain_y;  w0 = w / gain_x;  h0 = h / gain_y
+ *     the row is SUPPRESSED when  cx - 0.5f * w < lo_x  or  cy - 0.5f * h < lo_y  or
+ *     cx + 0.5f * w > hi_x  or  cy + 0.5f * h > hi_y  (tile-input pixels, strict comparisons: a side
+ *     on its bound stays; a NaN coordinate or bound suppresses nothing; -inf / +inf disables a side).
+ *     A suppressed row's box is un-mapped as usual and each of its nc scores is written as -1.0f; any
+ *     other row's scores are copied bit for bit (a NaN keeps its payload).  Nothing is clipped.
+ *   empty slot (tile == -1), and any tile outside [0, T): four zeros and nc scores of -1.0f.  The table
+ *     is device data that the host cannot see: the kernel checks the index and never reads outside pred.
+ * yms_det_candidates takes a pair only for score > conf with conf >= 0, so a -1 row is never a
+ * candidate, a kept detection or a voter; that is the whole suppression mechanism.
+ * One launch, no host read of device memory, no allocation: capture-safe.  YMS_ERR_INVALID: a NULL or
+ * not 4-byte aligned pointer, n outside 1..65535, S, A, nc or T < 1, A * (4+nc) > 2^31 - 1, or
+ * S * A * nc >= 2^31 (yms_det_candidates' limit on the merged rows).  Any nc >= 1: 16-byte accesses are
+ * used when 4+nc is a multiple of 4 and pred and out are 16-byte aligned, single floats otherwise.  out
+ * must not overlap pred or the table.  The launch has at most yms_tile_merge_max_blocks() blocks, each
+ * striding over (slot, 256-unit chunk) work items. */
+typedef struct {
+  int32_t tile;                          /* index into pred's first axis; -1 = empty slot */
+  float gain_x, gain_y, pad_x, pad_y;    /* orig = (v - pad) / gain for centres, v / gain for w, h */
+  float lo_x, lo_y, hi_x, hi_y;          /* suppression bounds in tile-input pixels */
+  int32_t reserved[3];                   /* 48-byte records; ignored */
+} yms_tile_slot;
+int yms_tile_merge_max_blocks(void);
+yms_status yms_tile_merge(int n, int S, int A, int nc, int T, const float* pred, const yms_tile_slot* table,
+                          float* out, void* stream);
 
 /* ---- optimizer step: SGD / Adam + weight EMA + norm clipping + non-finite skip ------------ */
 /* Replaces torch.optim.SGD / Adam behind tools/utils.py:11-25 get_optimizer, the

@@ -235,6 +235,8 @@ _SIGS = {
     "yms_det_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "yms_det_finalize_vote": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P]),
     "yms_tta_merge": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "yms_tile_merge_max_blocks": (_I, []),
+    "yms_tile_merge": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "yms_optim_chunk_elems": (_I, []),
     "yms_optim_table_chunks": (_L, [_I, _P]),
     "yms_optim_table_bytes": (_SZ, [_I, _P]),
