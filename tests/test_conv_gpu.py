@@ -376,3 +376,54 @@ def test_wgrad_workspace_smaller_than_planned(route, monkeypatch):
     st = L.lib().yms_conv_wgrad(sp, xb.data_ptr(), xb.shape[-1], 0, dzb.data_ptr(), dzb.shape[-1], 0, ws.data_ptr(),
                                 64, dw.data_ptr(), 0, L.stream_ptr())
     assert st != 0
+
+
+WG_ROUTES = {"default": {}, "tt": {"YMS_WG_HALO": "0", "YMS_WG_RING": "0"}, "ring": {"YMS_WG_HALO": "0", "YMS_WG_RING": "2"}}
+
+
+@pytest.mark.parametrize("sized", ["default", "tt"])
+@pytest.mark.parametrize("shp", [(2, 64, 24, 24, 64, 3, 1), (2, 128, 12, 12, 128, 1, 1)])
+def test_wgrad_workspace_from_another_route(shp, sized, monkeypatch):
+    """A workspace sized under one route and handed to a call that takes another.  sized = default (halo
+    for the 3x3 shape, ring for the 1x1), used with YMS_WG_HALO=0 YMS_WG_RING=0, then with YMS_WG_RING=2: a
+    larger workspace of another slab geometry.  sized = tt, used under the default route and the forced ring:
+    for the 3x3 shape the halo route plans three times the bytes it is given, so its splits have to shrink.
+    Each call either refuses or fits its splits into the bytes it was given and matches the fp32 torch
+    gradient; in both cases it writes nothing outside them.  The workspace is a slice of a larger tensor whose
+    other elements hold a sentinel; the part behind it is as large as the largest workspace any route asks."""
+    def use(env):
+        for k in ("YMS_WG_RING", "YMS_WG_HALO", "YMS_WG_HALO_NB2", "YMS_WG_SLAB_RATIO"):
+            monkeypatch.delenv(k, raising=False)
+        for name, v in env.items():
+            monkeypatch.setenv(name, v)
+
+    dtype = torch.bfloat16
+    n, cin, h, w, cout, k, s = shp
+    g = torch.Generator().manual_seed(n + cin + cout + k)
+    x = torch.randn(n, cin, h, w, generator=g)
+    shp_ = shape(n, h, w, cin, cout, k, s, dtype)
+    dz = torch.randn(n, cout, shp_.ho, shp_.wo, generator=g)
+    wr = torch.zeros(cout, cin, k, k, requires_grad=True)
+    F.conv2d(x.to(dtype).float(), wr, None, s, k // 2).backward(dz.to(dtype).float())
+    sp = ctypes.pointer(shp_)
+    xb, dzb = nhwc(x, dtype), nhwc(dz, dtype)
+    need = {}
+    for route, env in WG_ROUTES.items():
+        use(env)
+        need[route] = L.lib().yms_conv_wgrad_ws_bytes(sp)
+    wsb = need[sized]
+    assert wsb > 0 and wsb % 16 == 0 and min(need.values()) > 0
+    if sized == "tt" and k == 3:
+        assert need["default"] > 2 * wsb            # the direction in which an unfitted split count would overflow
+    sent, front, nws, back = -12345.0, 4096, wsb // 4, max(need.values()) // 4 + 4096
+    buf = torch.full((front + nws + back,), sent, dtype=torch.float32, device="cuda")
+    ws = buf[front:front + nws]
+    for route in [r for r in WG_ROUTES if r != sized]:
+        use(WG_ROUTES[route])
+        dw = torch.zeros(cout, cin, k, k, device="cuda")
+        st = L.lib().yms_conv_wgrad(sp, xb.data_ptr(), xb.shape[-1], 0, dzb.data_ptr(), dzb.shape[-1], 0,
+                                    ws.data_ptr(), wsb, dw.data_ptr(), 0, L.stream_ptr())
+        torch.cuda.synchronize()
+        if st == 0:
+            _close(dw.cpu(), wr.grad, 2e-3)
+        assert (buf[:front] == sent).all().item() and (buf[front + nws:] == sent).all().item(), (route, st)

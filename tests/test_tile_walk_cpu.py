@@ -9,15 +9,8 @@ per block, the stride-2 direct input gradient) is derived in tile_walk_cases.py.
 import pytest
 
 import tile_walk_cases as T
+from tile_walk_cases import cu_count  # noqa: F401  (fixture)
 from yms import _lib as L
-
-
-@pytest.fixture
-def cu_count():
-    """yms_cu_count_set(n) for the test, the process' setting restored after it."""
-    prev = L.lib().yms_cu_count_set(-1)
-    yield lambda n: L.lib().yms_cu_count_set(int(n))
-    L.lib().yms_cu_count_set(prev)
 
 
 def walks(tiles, grid):

@@ -20,20 +20,13 @@ import torch.nn.functional as F
 
 import tile_walk_cases as T
 from hiputil import DT, check_moments, nchw, nhwc, pack, r8, ref_conv, shape, split_stats, stats_buffer
+from tile_walk_cases import cu_count  # noqa: F401  (fixture)
 from test_conv_gpu import TOL, _close                     # 1e-2 / 2e-3 of max|ref| (bf16 / f16); dgrad twice that
 from yms import _lib as L
 
 pytestmark = pytest.mark.gpu
 GUARD = 3.0
 DEV = "cuda"
-
-
-@pytest.fixture
-def cu_count():
-    """yms_cu_count_set(n) for the test, the process' setting restored after it."""
-    prev = L.lib().yms_cu_count_set(-1)
-    yield lambda n: L.lib().yms_cu_count_set(int(n))
-    L.lib().yms_cu_count_set(prev)
 
 
 def _bits(t):

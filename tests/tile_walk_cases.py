@@ -11,6 +11,8 @@ Not covered, on purpose: the implicit-GEMM input gradient (stride 1 and the stri
 launches one block per tile (NT_DGRAD_MULT in conv_igemm.hip), so the CU count does not reach it."""
 import ctypes
 
+import pytest
+
 from hiputil import DT, shape
 from yms import _lib as L
 
@@ -18,6 +20,14 @@ OVERRIDES = (1, 3)              # conv forward / direct kernels
 DW_OVERRIDES = (1, 2, 3)        # depthwise (2: the multi-strip derivations below)
 WG_OVERRIDES = (1, 2048)        # split-K weight gradients: one split / as many as the work allows
 LOWP = ("bf16", "f16")
+
+
+@pytest.fixture
+def cu_count():
+    """yms_cu_count_set(n) for the test, the process' setting restored after it."""
+    prev = L.lib().yms_cu_count_set(-1)
+    yield lambda n: L.lib().yms_cu_count_set(int(n))
+    L.lib().yms_cu_count_set(prev)
 
 
 def cdiv(a, b):
@@ -213,12 +223,12 @@ def dw_ws_rows(shp, dt):
     return wsb // (k * k * c * 4)
 
 
-# ---- split-K weight gradients (TT in conv_igemm.hip, wgrad_ring.hip, wgrad_halo.hip) ---------------------
+# ---- split-K weight gradients (route and TT kernel in wgrad.hip, wgrad_ring.hip, wgrad_halo.hip) ---------
 # (n, cin, h, w, cout, k, stride); the route is forced with YMS_WG_RING / YMS_WG_HALO as test_conv_gpu.py does.
-# splits = min(work / minimum per split, ceil(4 CUs / tiles) (halo: ceil(2 CUs / tiles)), slab cap).  Every case
-# has >= 4 (halo: >= 2) tiles of its weight-gradient GEMM, so override 1 gives one split: one block per tile walks
-# every pixel.  Under 2048 the work bound decides: ceil(M / 32 / 16) (TT), ceil(M / 64 / 8) (ring), the patches
-# (halo), or the slab cap where that is lower.  The workspace is splits slabs (wg_slab_bytes).
+# wgrad_splits = min(work / minimum per split, ceil(4 CUs / tiles) (halo: ceil(2 CUs / tiles)), slab cap).  Every
+# case has >= 4 (halo: >= 2) tiles of its weight-gradient GEMM, so override 1 gives one split: one block per tile
+# walks every pixel.  Under 2048 the work bound decides: ceil(M / 32 / 16) (TT), ceil(M / 64 / 8) (ring), the
+# patches (halo), or the slab cap where that is lower.  The workspace is splits slabs (wg_slab_bytes).
 WG_ENV = {"tt": {"YMS_WG_RING": "0", "YMS_WG_HALO": "0"}, "ring": {"YMS_WG_RING": "2", "YMS_WG_HALO": "0"},
           "halo": {"YMS_WG_HALO": "2"}}
 WG_GEMM = [(2, 64, 40, 40, 128, 3, 1), (2, 200, 37, 39, 130, 1, 1), (2, 64, 40, 40, 64, 3, 1),
@@ -234,8 +244,9 @@ def wg_ws_bytes(shp, dt):
 
 
 def wg_slab_bytes(route, shp):
-    """one split's fp32 slab: the weight gradient rounded up to the route's tiles (wgrad_plan, wgrad_ring_plan,
-    wgrad_halo_plan: 32- or 64-output-channel blocks, the 32-channel one with a slab per k-half)"""
+    """one split's fp32 slab(s), WgradRoute's slabs_per_split x slab_rows x slab_ld of wgrad.hip: the weight
+    gradient rounded up to the route's tiles (wgrad_plan there, wgrad_ring_plan, wgrad_halo_plan: 32- or
+    64-output-channel blocks, the 32-channel one with a slab per k-half)"""
     n, cin, h, w, cout, k, s = shp
     cin8 = cdiv(cin, 8) * 8
     kf = k * k * cin8

@@ -1,5 +1,5 @@
 """Summarise hipcc -Rpass-analysis=kernel-resource-usage for a .hip file (dev tool).
-usage: python tools/kres.py yolo-ms_amd/csrc/conv_igemm.hip [filter]"""
+usage: python tools/kres.py yolo-ms_amd/csrc/wgrad.hip [filter]"""
 import re
 import subprocess
 import sys

@@ -1,5 +1,5 @@
 // Device helpers shared by the convolution kernels (conv_igemm.hip, conv_direct.hip, stem.hip,
-// wgrad_*.hip, dwconv.hip): MFMA wrappers, counted vmcnt waits, the raw barrier,
+// wgrad*.hip, dwconv.hip): MFMA wrappers, counted vmcnt waits, the raw barrier,
 // raw-buffer LDS-DMA and the XCD-aware block remap.
 #pragma once
 #include "yms_common.hpp"
@@ -147,5 +147,18 @@ __device__ __forceinline__ void merge_moments(const float* s, const float* m, in
 
 // host: CU count of the current device (persistent grids)
 int conv_cu_count();
+
+// host: argument checks of the convolution entry points (conv_igemm.hip, wgrad.hip)
+inline int elem_size(int dt) { return dt == YMS_F32 ? 4 : 2; }
+inline bool shape_ok(const yms_conv_shape* s) {
+  if (!s || s->n <= 0 || s->h <= 0 || s->w <= 0 || s->cin <= 0 || s->cout <= 0) return false;
+  if (!(s->k == 1 || s->k == 3) || !(s->stride == 1 || s->stride == 2)) return false;
+  if (s->dtype < 0 || s->dtype > 2) return false;
+  if (s->ho != (s->h + 2 * s->pad - s->k) / s->stride + 1) return false;
+  if (s->wo != (s->w + 2 * s->pad - s->k) / s->stride + 1) return false;
+  if ((long)s->n * s->h * s->w >= (1l << 31) || (long)s->n * s->ho * s->wo >= (1l << 31)) return false;
+  return true;
+}
+inline bool view_ok(int ld, int off, int c) { return ld % 8 == 0 && off % 8 == 0 && off + c <= ld; }
 
 }  // namespace yms

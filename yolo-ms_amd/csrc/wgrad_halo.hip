@@ -3,7 +3,7 @@
 //
 //   dW[co][tap][ci] = sum_p dz[p][co] * x[src(p, tap)][ci]     (yolov8/model/components.py:72 backward)
 //
-// The im2col TT kernel (conv_igemm.hip) gathers every input pixel nine times through L2 (once
+// The im2col TT kernel (wgrad.hip) gathers every input pixel nine times through L2 (once
 // per tap) and re-reads dz once per tap-column tile; with two register-staged k-tiles of 32
 // pixels in flight it also leaves the streaming layers (160^2 / 320^2 maps, 32-64 channels)
 // at 0.6-1.4 TB/s.  Here a block owns (32*MB output channels) x (all 9 taps x 32*NB input
@@ -20,11 +20,9 @@
 //     block keeps 3 * MB * NB * WK waves busy without a second staged patch;
 //   * blocks of one pixel split are consecutive logical ids (XCD-remapped, shared L2) and write
 //     one fp32 partial slab each, reduced in a fixed order by wgrad_reduce_kernel.
-#include "conv_common.hpp"
 #include "wgrad_halo.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace yms {
 
@@ -218,11 +216,6 @@ void conv_wgrad_halo_kernel(WHParams p) {
   }
 }
 
-static int env_int_wh(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // patch width: the whole output row when it is narrow, else a divisor of it near 32
 static int pick_tw(int ow) {
   if (ow <= 40) return ow;
@@ -232,7 +225,7 @@ static int pick_tw(int ow) {
 }
 
 bool wgrad_halo_plan(const yms_conv_shape* s, WHPlan* w) {
-  const int on = env_int_wh("YMS_WG_HALO", 1);   // read per call: tests switch it at run time
+  const int on = env_int("YMS_WG_HALO", 1);
   if (!on || s->k != 3 || s->pad != 1 || s->dtype == YMS_F32) return false;
   // measured on every 3x3 layer of YOLOv8-s at B=64 (profiles/r03_wgrad_halo_micro.txt): the halo
   // kernel wins where the output channels fill its 32 / 64-channel blocks exactly (160^2
@@ -258,7 +251,7 @@ bool wgrad_halo_plan(const yms_conv_shape* s, WHPlan* w) {
   // seven such layers, profiles/r06_wgrad_pmc_layers.txt); one block covering all 64 input
   // channels (12 waves) reads dz once, on 64-pixel patches of 4 x 16 (halo 6 x 18 = 1.69x)
   if (q.S == 1 && q.mb == 2 && rup(s->cin, 8) == 64 && s->wo % 16 == 0 && s->ho >= 4 &&
-      env_int_wh("YMS_WG_HALO_NB2", 1)) {
+      env_int("YMS_WG_HALO_NB2", 1)) {
     q.nb = 2;
     q.kp = 64;
     q.hb = 128;
@@ -282,17 +275,11 @@ bool wgrad_halo_plan(const yms_conv_shape* s, WHPlan* w) {
   q.tiles_ci = cdiv(cin8, 32 * q.nb);
   q.slab_rows = q.tiles_co * 32 * q.mb;
   q.slab_ld = 9 * cin8;
-  const int tiles = q.tiles_co * q.tiles_ci;
-  // about two blocks per CU in all; each split writes (and the reduce re-reads) one fp32 slab, so
-  // cap the slab round trip at the layer's own x + dz bytes (keeping >= 256 blocks)
-  int splits = std::max(1, std::min(q.npatch, cdiv(2l * conv_cu_count(), tiles)));
+  // about two blocks per CU in all, at least one patch per split; a split of the 32-output-channel
+  // variant writes wk slabs
   const double data = (double)s->n * s->ho * s->wo * rup(s->cout, 8) * 2.0 + (double)s->n * s->h * s->w * cin8 * 2.0;
   const double slab_rt = 2.0 * 4.0 * (double)q.slab_rows * q.slab_ld * q.wk;
-  const double ratio = getenv("YMS_WG_SLAB_RATIO") ? atof(getenv("YMS_WG_SLAB_RATIO")) : 0.05;   // see conv_igemm.hip
-  const int cap = std::max((int)(ratio * data / slab_rt), cdiv(256, tiles));
-  splits = std::max(1, std::min(splits, cap));
-  q.pps = cdiv(q.npatch, splits);
-  q.splits = cdiv(q.npatch, q.pps);
+  q.want_splits = wgrad_splits(q.npatch, q.tiles_co * q.tiles_ci, 2, data, slab_rt);
   *w = q;
   return true;
 }
@@ -315,29 +302,20 @@ static void dispatch_wh(const WHPlan& w, const WHParams& p, int blocks, hipStrea
   }
 }
 
-yms_status wgrad_halo_launch(const yms_conv_shape* s, const WHPlan& w, const void* x, int x_ld, int x_off,
-                             const void* dz, int dz_ld, int dz_off, float* slab, hipStream_t st) {
+yms_status wgrad_halo_launch(const yms_conv_shape* s, const WHPlan& w, const WgradArgs& a, hipStream_t st) {
   WHParams p{};
-  p.x = (const char*)x;
-  p.dz = (const char*)dz;
-  p.slab = slab;
-  p.x_ld = x_ld; p.x_off = x_off; p.dz_ld = dz_ld; p.dz_off = dz_off;
-  const long es = 2;
-  const long dzb = (long)s->n * s->ho * s->wo * dz_ld * es, xb = (long)s->n * s->h * s->w * x_ld * es;
-  if (dzb >= (1l << 31) - (1l << 20) || xb >= (1l << 31) - (1l << 20)) return YMS_ERR_UNSUPPORTED;
-  p.dz_bytes = (uint32_t)dzb;
-  p.x_bytes = (uint32_t)xb;
+  if (!wgrad_operands(p, s, a)) return YMS_ERR_UNSUPPORTED;
   p.H = s->h; p.W = s->w; p.OH = s->ho; p.OW = s->wo; p.pad = s->pad;
   p.cin8 = (int)rup(s->cin, 8);
   p.cout8 = (int)rup(s->cout, 8);
   p.TW = w.TW; p.R = w.R; p.HC = w.HC; p.HPX = w.HR * w.HC; p.RTW = w.R * w.TW;
-  p.ptx = w.ptx; p.pty = w.pty; p.npatch = w.npatch; p.pps = w.pps;
+  p.ptx = w.ptx; p.pty = w.pty; p.npatch = w.npatch; p.pps = a.per;
   p.tiles_co = w.tiles_co; p.tiles_ci = w.tiles_ci; p.slab_rows = w.slab_rows; p.slab_ld = w.slab_ld;
   p.div_tw = make_fastdiv(w.TW);
   p.div_hc = make_fastdiv(w.HC);
   p.div_ptx = make_fastdiv(w.ptx);
   p.div_pp = make_fastdiv(w.ptx * w.pty);
-  const int blocks = w.tiles_co * w.tiles_ci * w.splits;
+  const int blocks = w.tiles_co * w.tiles_ci * a.splits;
   if (s->dtype == YMS_BF16) dispatch_wh<bf16>(w, p, blocks, st);
   else dispatch_wh<f16>(w, p, blocks, st);
   return launch_status();

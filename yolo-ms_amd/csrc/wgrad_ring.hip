@@ -3,7 +3,7 @@
 //
 //   dW[co][tap * cin8 + ci] = sum_p dz[p][co] * x[src(p, tap)][ci]    (components.py:72 backward)
 //
-// The register-staged TT kernel (conv_igemm.hip, conv_wgrad_kernel) keeps one 32-pixel k-tile
+// The register-staged TT kernel (wgrad.hip, conv_wgrad_kernel) keeps one 32-pixel k-tile
 // per block in flight and round-trips it through VGPRs; it measured 0.08 of the bf16 MFMA peak
 // inside the training step.  Here:
 //   * a block owns a BM (output channels) x BN (im2col columns) tile and a contiguous pixel range
@@ -20,11 +20,9 @@
 //   * blocks of one pixel split are consecutive logical ids (XCD-remapped: they share dz rows and
 //     im2col pixels in one L2) and write one fp32 partial slab each, summed in a fixed order by
 //     wgrad_reduce_kernel (deterministic).
-#include "conv_common.hpp"
 #include "wgrad_ring.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace yms {
 
@@ -204,15 +202,10 @@ __global__ __launch_bounds__(512, OCC) void conv_wgrad_ring_kernel(WRParams p) {
       }
 }
 
-static int env_int_wr(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // 64-pixel k-tiles, 2 stages, 2 blocks per CU (round 4, measured and dropped: 32-pixel k-tiles with
 // 2 / 4 stages, 3 stages at 1 block per CU, and the 64 x 64 GEMMs on zero-filled 64 x 128 tiles)
 bool wgrad_ring_plan(const yms_conv_shape* s, WRPlan* w) {
-  const int on = env_int_wr("YMS_WG_RING", 1);   // read per call: tests switch it at run time
+  const int on = env_int("YMS_WG_RING", 1);
   if (!on || s->dtype == YMS_F32 || (s->k != 1 && s->k != 3)) return false;
   WRPlan q{};
   q.cin8 = (int)rup(s->cin, 8);
@@ -233,17 +226,10 @@ bool wgrad_ring_plan(const yms_conv_shape* s, WRPlan* w) {
   const long M = (long)s->n * s->ho * s->wo;
   if (M >= (1l << 30)) return false;
   q.nkt = cdiv(M, q.kp);
-  const int blocks = q.tiles_m * q.tiles_n;
-  // about 4 blocks per CU, at least 8 k-tiles per split; the slab round trip capped at a fraction
-  // of the layer's own x + dz bytes (keeping >= 256 blocks), as for the register-staged kernel
-  int splits = std::max(1, std::min(cdiv(q.nkt, 8), cdiv(4l * conv_cu_count(), blocks)));
+  // about 4 blocks per CU, at least 8 k-tiles per split
   const double data = (double)M * (double)(rup(s->cout, 8) + q.cin8) * 2.0;
   const double slab_rt = 2.0 * 4.0 * (double)q.slab_rows * (double)q.slab_ld;
-  const double ratio = getenv("YMS_WG_SLAB_RATIO") ? atof(getenv("YMS_WG_SLAB_RATIO")) : 0.05;   // see conv_igemm.hip
-  const int cap = std::max((int)(ratio * data / slab_rt), cdiv(256, blocks));
-  splits = std::max(1, std::min(splits, cap));
-  q.kt_per_split = cdiv(q.nkt, splits);
-  q.splits = cdiv(q.nkt, q.kt_per_split);
+  q.want_splits = wgrad_splits(cdiv(q.nkt, 8), q.tiles_m * q.tiles_n, 4, data, slab_rt);
   *w = q;
   return true;
 }
@@ -260,28 +246,18 @@ static void launch_wr_k(const WRPlan& w, const WRParams& p, dim3 grid, hipStream
   else launch_wr_t<T, KS, 128, 64>(w, p, grid, st);
 }
 
-yms_status wgrad_ring_launch(const yms_conv_shape* s, const WRPlan& w, const void* x, int x_ld, int x_off,
-                             const void* dz, int dz_ld, int dz_off, float* slab, hipStream_t st) {
+yms_status wgrad_ring_launch(const yms_conv_shape* s, const WRPlan& w, const WgradArgs& a, hipStream_t st) {
   WRParams p{};
-  p.x = (const char*)x;
-  p.dz = (const char*)dz;
-  p.slab = slab;
-  p.x_ld = x_ld; p.x_off = x_off; p.dz_ld = dz_ld; p.dz_off = dz_off;
-  const long es = 2;
-  const long M = (long)s->n * s->ho * s->wo;
-  const long dzb = M * dz_ld * es, xb = (long)s->n * s->h * s->w * x_ld * es;
-  if (dzb >= (1l << 31) - (1l << 20) || xb >= (1l << 31) - (1l << 20)) return YMS_ERR_UNSUPPORTED;
-  p.dz_bytes = (uint32_t)dzb;
-  p.x_bytes = (uint32_t)xb;
+  if (!wgrad_operands(p, s, a)) return YMS_ERR_UNSUPPORTED;
   p.SH = s->h; p.SW = s->w; p.stride = s->stride; p.pad = s->pad;
   p.cout8 = (int)rup(s->cout, 8);
-  p.cpt = w.cpt; p.Kc = w.kc; p.M = (int)M;
-  p.nkt = w.nkt; p.kt_per_split = w.kt_per_split;
+  p.cpt = w.cpt; p.Kc = w.kc; p.M = s->n * s->ho * s->wo;
+  p.nkt = w.nkt; p.kt_per_split = a.per;
   p.tiles_n = w.tiles_n; p.tiles_mn = w.tiles_m * w.tiles_n;
   p.slab_rows = w.slab_rows; p.slab_ld = w.slab_ld;
   p.div_ow = make_fastdiv(s->wo);
   p.div_ohw = make_fastdiv(s->ho * s->wo);
-  const dim3 grid((unsigned)(w.tiles_m * w.tiles_n * w.splits));
+  const dim3 grid((unsigned)(w.tiles_m * w.tiles_n * a.splits));
   if (s->dtype == YMS_BF16) {
     if (s->k == 1) launch_wr_k<bf16, 1>(w, p, grid, st); else launch_wr_k<bf16, 3>(w, p, grid, st);
   } else {
